@@ -12,11 +12,19 @@ gathered to rank 0 over RCCL).
 processes itself (before the parent touches a GPU); under torchrun it is one of them.
 
 Prints ONE JSON line on rank 0.  `roofline` is computed for the persistent loop kernel from
-HIP events around its launch; `roofline.traffic` from two rocprofv3 --pmc passes (FETCH_SIZE,
-WRITE_SIZE) of this same script run as child processes before the measured run (N = 1; the
-committed profile is the labelled fallback); `cpu_baseline` times the reference's own op
-sequence as a PyTorch-CPU eager restatement (oracle/torch_cpu.py) on this host's cores over a
-bounded slice of the same workload.
+HIP events around its launch.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: set
+up, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR` also writes the audio of the
+last timed step (what generate() returned) as DIR/<name>.npy; the inputs, weights and Philox keys
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+Everything else runs only with `--full`: `roofline.traffic` from two rocprofv3 --pmc passes
+(FETCH_SIZE, WRITE_SIZE) of this same script run as child processes before the measured run
+(N = 1; a summary named by WRNN_PMC_PROFILE is the labelled fallback); the `fold_batched` line;
+`other_configs` (BASELINE configs 1 / 3 / 4 / 5 and the 8- / 32-stream serving lines);
+`cpu_baseline`, which times the reference's own op sequence as a PyTorch-CPU eager restatement
+(oracle/torch_cpu.py) on this host's cores over a bounded slice of the same workload.
 """
 from __future__ import annotations
 
@@ -454,7 +462,38 @@ def parse_args(argv=None):
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stub", action="store_true",
                     help="no GPU: gloo ranks time a stand-in generation (tests of the launcher / timing contract)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the PMC passes, the fold-batched line, the other "
+                         "configs and the CPU baselines (each still switched by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the audio of the last timed step as DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if not args.full and not args.pmc_child:
+        # a plain run is the headline alone
+        args.cpu_steps = args.other_configs = args.fold_batched = args.pmc = 0
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> None:
+    """arrays {name: array} as dirpath/<name>.npy in float64, at most DUMP_MAX_BYTES in all: a
+    larger array is cut to a fixed (seeded) sample of its elements, in their original order."""
+    os.makedirs(dirpath, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays)) // 8
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > budget:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, budget, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
+def audio_arrays(gathered, world: int) -> dict:
+    """Names of the dumped audio: `audio` on one GPU, `audio_rank<r>` per rank otherwise."""
+    if world == 1:
+        return {"audio": gathered[0]}
+    return {f"audio_rank{r}": a for r, a in enumerate(gathered)}
 
 
 def timed_steps(step, steps: int, warmup: int, world: int, dev):
@@ -489,15 +528,17 @@ def stub_main(args, world, rank):
     if world > 1:
         dist.init_process_group("gloo")
     from wavernn_amd import sharding
+    last = {}
 
     def step(i):
         time.sleep(0.01)
         out = np.zeros(22050)
-        if world > 1:
-            sharding.gather_audio({rank: out}, world, dev)
+        last["audio"] = sharding.gather_audio({rank: out}, world, dev) if world > 1 else [out]
         return out.shape[0]
 
     elapsed, total = timed_steps(step, args.steps, args.warmup, world, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, audio_arrays(last["audio"], world))
     sharded = sharded_configs(dev, world, rank, stub=True) if args.other_configs else {}
     if rank == 0:
         print(json.dumps({"metric": "stub", "value": total / elapsed, "unit": "samples/s", "n_gpus": world,
@@ -524,9 +565,9 @@ def main():
     if args.pmc_child:
         args.steps, args.warmup, args.cpu_steps, args.fold_batched, args.pmc = 1, 0, 0, 0, 0
     # HBM traffic passes first, while this process has not touched the GPU (child processes)
-    traffic, traffic_from = None, None
+    traffic, traffic_from = None, None if args.full else "not measured: a plain run (--full runs the live passes)"
     headline_shape = not args.batched and args.mode == "MOL" and abs(args.seconds - 5.0) < 1e-9
-    if rank == 0 and headline_shape and not args.pmc_child:
+    if rank == 0 and headline_shape and args.full and not args.pmc_child:
         # rank 0 only (its GPU = the children's cuda:0); the other ranks wait in the rendezvous
         live = pmc_live() if args.pmc else None
         traffic, traffic_from = resolve_traffic(live, PMC_PROFILE)
@@ -544,7 +585,7 @@ def main():
     T = syn.frames_for_seconds(args.seconds, d.sample_rate, d.hop_length)
     mel = torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=1 + rank))[None]
     target, overlap = 11000, 550
-    loop_ms = []
+    loop_ms, last = [], {}
 
     from wavernn_amd import sharding
 
@@ -553,13 +594,14 @@ def main():
         # the finished audio is gathered to rank 0 — the path's only collective
         g = i * world + rank
         out = model.generate(mel, None, args.batched, target, overlap, True, seed=1000, row_offset=g, verbose=False)
-        if world > 1:
-            sharding.gather_audio({rank: out}, world, dev)
+        last["audio"] = sharding.gather_audio({rank: out}, world, dev) if world > 1 else [out]
         if i >= 0:
             loop_ms.append(model.loop_handle().elapsed_ms())
         return out.shape[0]
 
     elapsed, total_samples = timed_steps(step, args.steps, args.warmup, world, dev)
+    if rank == 0 and args.dump_outputs and not args.pmc_child:
+        dump_outputs(args.dump_outputs, audio_arrays(last["audio"], world))
     lm = torch.tensor([float(np.mean(loop_ms))], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(lm, op=dist.ReduceOp.MAX)

@@ -40,11 +40,25 @@ def test_bench_single_rank_default():
 
 
 @pytest.mark.parametrize("n", [1, 2])
+def test_bench_plain_run_dumps_the_last_step(n, tmp_path):
+    """Without --full the line is the headline alone (no other config is run), and --dump-outputs
+    writes what the last timed step returned: one float64 array per rank, gathered on rank 0."""
+    import numpy as np
+    rec = _run(["--gpus", str(n), "--steps", "2", "--warmup", "0", "--stub", "--dump-outputs", str(tmp_path / "out")])
+    assert rec["other_configs"] == {} and rec["steps"] == 2 and rec["ms_per_step"] >= 10.0
+    names = ["audio.npy"] if n == 1 else [f"audio_rank{r}.npy" for r in range(n)]
+    assert sorted(os.listdir(tmp_path / "out")) == names
+    for name in names:
+        a = np.load(tmp_path / "out" / name)
+        assert a.dtype == np.float64 and a.shape == (22050,) and not a.any()
+
+
+@pytest.mark.parametrize("n", [1, 2])
 def test_bench_sharded_legs(n):
     """Configs 4 and 5 as BASELINE states them (utterances sharded over the ranks): at every N the
     line carries both legs with the same keys; utterances = per-rank share x N, samples summed
     over the ranks (gathered on rank 0) over the max-over-ranks time."""
-    rec = _run(["--gpus", str(n), "--steps", "1", "--warmup", "0", "--stub"])
+    rec = _run(["--gpus", str(n), "--steps", "1", "--warmup", "0", "--stub", "--full"])
     oc = rec["other_configs"]
     keys = {"samples_per_s", "rtf", "rtf_per_gpu", "utterances", "n_gpus", "rows_per_gpu", "loop_steps", "device_ms",
             "wall_s", "us_per_loop_step", "loop_samples_per_s", "kernel_path", "roofline", "note"}
