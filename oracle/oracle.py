@@ -16,6 +16,7 @@ tests/golden/make_golden.py) in tests/test_oracle_golden.py.
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import math
 import os
 import subprocess
@@ -25,6 +26,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_build", "liboracle.so")
+STAMP_PATH = LIB_PATH + ".sha256"
 
 _F = ctypes.POINTER(ctypes.c_float)
 _I32 = ctypes.POINTER(ctypes.c_int32)
@@ -65,15 +67,31 @@ _DM_KEYS = {
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the C restatement (gcc, no GPU toolchain involved)."""
+    """Compile the C restatement (gcc, no GPU toolchain involved).
+
+    The library is rebuilt whenever the source or the compile line differs from what built it: a
+    SHA-256 of both is kept beside it (file times do not survive a copy of the tree, and a stale
+    library with another orc_fatchord_loop signature would be called with the wrong arguments).
+    The new library replaces the old one by rename, so a process that has the old one mapped
+    keeps a valid mapping."""
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
     src = os.path.join(HERE, "wavernn_oracle.c")
-    if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= os.path.getmtime(src):
-        return LIB_PATH
-    cmd = ["gcc", "-O3", "-fPIC", "-shared", "-fno-fast-math", "-o", LIB_PATH, src, "-lm"]
+    cmd = ["gcc", "-O3", "-fPIC", "-shared", "-fno-fast-math", "-o", LIB_PATH + ".tmp", src, "-lm"]
+    with open(src, "rb") as f:
+        want = hashlib.sha256(" ".join(cmd[:-3]).encode() + b"\0" + f.read()).hexdigest()
+    if os.path.exists(LIB_PATH):
+        try:
+            with open(STAMP_PATH) as f:
+                if f.read().strip() == want:
+                    return LIB_PATH
+        except OSError:
+            pass
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)
+    os.replace(LIB_PATH + ".tmp", LIB_PATH)
+    with open(STAMP_PATH, "w") as f:
+        f.write(want + "\n")
     return LIB_PATH
 
 
@@ -87,7 +105,7 @@ def lib():
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.orc_fatchord_loop.restype = ctypes.c_int
         _lib.orc_fatchord_loop.argtypes = [ctypes.POINTER(_Dims), ctypes.POINTER(_Weights), _F, _F,
-                                           ctypes.c_int, ctypes.c_int, _F, _F, _I32]
+                                           ctypes.c_int, ctypes.c_int, _F, _F, _I32, _F]
         _lib.orc_deepmind_loop.restype = ctypes.c_int
         _lib.orc_deepmind_loop.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_DMWeights),
                                            ctypes.c_int, ctypes.c_int, _F, _I32, _I32]
@@ -99,11 +117,12 @@ def _fp(a: np.ndarray):
 
 
 def fatchord_loop(state: Dict[str, np.ndarray], mode: str, mels: np.ndarray, aux: np.ndarray,
-                  noise: np.ndarray) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+                  noise: np.ndarray, want_logits: bool = False):
     """Run the reference loop (fatchord_version.py:201-237) on folded conditioning.
 
     mels [B][L][feat], aux [B][L][4·aux_dims], noise [L][B][K] → (samples [B][L] f32,
-    labels [B][L] int32 or None)."""
+    labels [B][L] int32 or None); with want_logits also the fc3 output [B][L][n_classes] that
+    each step's sampler read, as a third element."""
     mels = np.ascontiguousarray(mels, dtype=np.float32)
     aux = np.ascontiguousarray(aux, dtype=np.float32)
     noise = np.ascontiguousarray(noise, dtype=np.float32)
@@ -119,12 +138,14 @@ def fatchord_loop(state: Dict[str, np.ndarray], mode: str, mels: np.ndarray, aux
     d = _Dims(rnn, fc, a, feat, nc, mol)
     out = np.zeros((B, L), np.float32)
     labels = None if mol else np.zeros((B, L), np.int32)
+    logits = np.zeros((B, L, nc), np.float32) if want_logits else None
     rc = lib().orc_fatchord_loop(ctypes.byref(d), ctypes.byref(w), _fp(mels), _fp(aux), B, L,
                                  _fp(noise), _fp(out),
-                                 labels.ctypes.data_as(_I32) if labels is not None else None)
+                                 labels.ctypes.data_as(_I32) if labels is not None else None,
+                                 _fp(logits) if logits is not None else None)
     if rc != 0:
         raise MemoryError("oracle allocation failed")
-    return out, labels
+    return (out, labels, logits) if want_logits else (out, labels)
 
 
 def deepmind_loop(state: Dict[str, np.ndarray], B: int, L: int, noise: np.ndarray):
