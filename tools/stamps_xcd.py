@@ -23,7 +23,9 @@ SPARSE_STAMPS = [(0, "start (after B1)"), (1, "GRU1 done (after B2)"), (2, "Y pu
                  (6, "w0: F2 published (+3 hand-offs)"), (7, "F2 gathered"), (8, "sample done"),
                  (9, "w1: GH1 terms + h2 published"), (10, "w4: h2 gathered"), (11, "w5: S quarter gathered"),
                  (13, "w5: GH2 done"), (12, "w7: ring done")]
-STAMPS = [(0, "start (after B1)"), (1, "GRU1 done (after B2)"), (2, "Y published (GRU2)"), (3, "w1: Y gathered"),
+# dense kernel: GRU2 + the y publish on waves 0, 5..7 (stamp 2: wave 0), fc1 / the Y poll on waves 1, 2,
+# fc2 / the F1 poll on waves 3, 4, the sampler on wave 0 (fatchord_xcd.h)
+STAMPS = [(0, "start (after B1)"), (1, "GRU1 done (after B2)"), (2, "w0: Y published (GRU2)"), (3, "w1: Y gathered"),
           (4, "w1: f1 published"), (5, "w3: F1 gathered"), (6, "w3: F2 published"), (7, "F2 gathered"),
           (8, "sample done"), (9, "w3: GH1 terms published"), (10, "w6: h2 gathered"),
           (14, "w5: S quarter gathered"), (12, "w7: ring done"), (11, "w1: S quarter + GH2 done"),

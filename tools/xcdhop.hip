@@ -7,6 +7,11 @@
 // Poll variants (LOCAL): 8-byte loads (8 per lane) or 16-byte buffer loads (4 per lane), one or
 // two poll rounds in flight, with or without draining the own publish first, with or without
 // the other waves of the workgroup streaming LDS (the XCD kernel's off-critical dots).
+// PACED rows: one barrier-paced hop per step as in the XCD kernel; their pollers (waves 1..POLLW) are
+// publishers too and drain their own store before the first poll.  ROLES rows: the same hop with
+// publishers and pollers on different waves (4 publishing waves, one per SIMD, pollers in flight
+// from the barrier or from an LDS flag) against 8 publishing waves with publishing pollers, after a
+// spin of GRU2's length; subtract the "no hop" row of the same spin.
 //   hipcc --offload-arch=gfx950 -O3 tools/xcdhop.hip -o tools/xcdhop && tools/xcdhop
 #include <hip/hip_runtime.h>
 
@@ -229,6 +234,94 @@ void run_paced(unsigned long long *vec, int *ctr, unsigned long long *out, const
     fflush(stdout);
 }
 
+// Role-split variant (the Y hop with publishers and pollers on different waves): per hop,
+// __syncthreads, then the publisher waves spin SPIN shader cycles (GRU2's length) and store the
+// workgroup's 16 granules; waves 1, 2 poll the whole vector (16-byte loads, 4 per lane).
+//   PUBW = 4: waves 0, 5, 6, 7 (one per SIMD) publish 4 granules each; waves 1, 2 publish
+//             nothing and poll from the barrier on (GATE 0) or from an LDS flag that wave 0 sets
+//             as it issues its store (GATE 1)
+//   PUBW = 8: all eight waves publish 2 granules each; the pollers drain their own store
+//             (vmcnt(0)) before the first poll, as in hops_paced
+//   PUBW = 0: nobody publishes or polls: the two barriers and the spin alone (the baseline to
+//             subtract)
+template <int PUBW, int SPIN, bool GATE>
+__global__ __launch_bounds__(512) void hops_roles(unsigned long long *vec, int *ctr, int nhops, unsigned long long *out) {
+    __shared__ int s_idx;
+    __shared__ int s_flag;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) {
+        int idx = -1;
+        if (xcc_id() == 0) idx = atomicAdd(ctr, 1);
+        s_idx = idx < kN ? idx : -1;
+        s_flag = 0;
+    }
+    __syncthreads();
+    const int me = s_idx;
+    if (me < 0) return;
+    const unsigned long long deadline = __builtin_amdgcn_s_memrealtime() + 200000000ull;
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    bool dead = false;
+    const bool poller = PUBW != 0 && (wave == 1 || wave == 2);
+    const int slot = PUBW == 8 ? wave : wave == 0 ? 0 : wave >= 5 ? wave - 4 : -1;   // publisher index
+    constexpr int per = PUBW ? kLine / PUBW : 0;
+    for (int h = 1; h <= nhops; ++h) {
+        __syncthreads();
+        unsigned long long *v = vec + (size_t)(h & 1) * kN * kLine;
+        if (PUBW == 0 || slot >= 0) {
+            if (SPIN) {
+                const unsigned long long s0 = __builtin_amdgcn_s_memtime();
+                while (__builtin_amdgcn_s_memtime() - s0 < (unsigned long long)SPIN) {
+                }
+            }
+            if (PUBW != 0 && lane < per) {
+                const int i = me * kLine + slot * per + lane;
+                __hip_atomic_store(v + i, ((unsigned long long)h << 32) | (unsigned)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            if (GATE && wave == 0 && lane == 0) __hip_atomic_store(&s_flag, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        if (poller) {
+            if (PUBW == 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (GATE) {
+                while (__hip_atomic_load(&s_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != h) __builtin_amdgcn_s_sleep(1);
+            }
+            const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(v, 0, 0x7fffffff, 0x00020000);
+            for (;;) {
+                u4v a[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) a[k] = ld16(r, 16 * (lane + 64 * k));
+                bool ok = true;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ok &= (a[k].y == (unsigned)h) & (a[k].w == (unsigned)h);
+                if (__all(ok)) break;
+                if (__builtin_amdgcn_s_memrealtime() > deadline) { dead = true; break; }
+            }
+        }
+        __syncthreads();
+        if (__syncthreads_or(dead)) break;
+    }
+    if (threadIdx.x == 64) out[me] = dead ? ~0ull : __builtin_amdgcn_s_memrealtime() - t0;
+}
+
+template <int PUBW, int SPIN, bool GATE>
+void run_roles(unsigned long long *vec, int *ctr, unsigned long long *out, const char *name) {
+    const int nhops = 20000;
+    hipMemset(vec, 0, 1 << 20);
+    hipMemset(ctr, 0, 4);
+    hipMemset(out, 0, kN * 8);
+    hipLaunchKernelGGL((hops_roles<PUBW, SPIN, GATE>), dim3(256), dim3(512), 0, 0, vec, ctr, nhops, out);
+    hipDeviceSynchronize();
+    unsigned long long h[kN];
+    hipMemcpy(h, out, kN * 8, hipMemcpyDeviceToHost);
+    unsigned long long mx = 0;
+    bool dead = false;
+    for (int i = 0; i < kN; ++i) {
+        if (h[i] == ~0ull) dead = true;
+        else if (h[i] > mx) mx = h[i];
+    }
+    printf("%-52s %s %.3f us per paced hop\n", name, dead ? "TIMEOUT" : "", mx * 10e-3 / nhops);
+    fflush(stdout);
+}
+
 // Poll round trip: wave 0 of 32 workgroups of one XCD polls a vector that never completes,
 // NR rounds of 4 x 16-byte sc1 loads (each round waits for the previous one)
 __global__ __launch_bounds__(512) void poll_rtt(unsigned long long *vec, int *ctr, unsigned long long *out) {
@@ -296,6 +389,17 @@ int main() {
         run_paced<8, 1, false, 3, 512>(vec, ctr, out, "PACED 8 pub, 1 poller, lines 4 KiB apart");
         run_paced<1, 1, false, 3, 128>(vec, ctr, out, "PACED 1 pub, 1 poller, lines 1 KiB apart");
         run_paced<8, 1, false, 3>(vec, ctr, out, "PACED 8 publisher waves, 1 poller (again)");
+        // role split: three barriers per hop in every ROLES row (subtract the "no hop" row of the same spin)
+        run_roles<0, 0, false>(vec, ctr, out, "ROLES no hop (barriers only), spin 0");
+        run_roles<8, 0, false>(vec, ctr, out, "ROLES 8 pub (pollers publish, drain), spin 0");
+        run_roles<4, 0, false>(vec, ctr, out, "ROLES 4 pub, pollers poll from the barrier, spin 0");
+        run_roles<4, 0, true>(vec, ctr, out, "ROLES 4 pub, pollers gated on LDS flag, spin 0");
+        run_roles<0, 700, false>(vec, ctr, out, "ROLES no hop (barriers only), spin 700");
+        run_roles<8, 700, false>(vec, ctr, out, "ROLES 8 pub (pollers publish, drain), spin 700");
+        run_roles<4, 700, false>(vec, ctr, out, "ROLES 4 pub, pollers poll from the barrier, spin 700");
+        run_roles<4, 700, true>(vec, ctr, out, "ROLES 4 pub, pollers gated on LDS flag, spin 700");
+        run_roles<8, 700, false>(vec, ctr, out, "ROLES 8 pub (pollers publish, drain), spin 700 (again)");
+        run_roles<4, 700, false>(vec, ctr, out, "ROLES 4 pub, pollers from the barrier, spin 700 (again)");
     }
     return 0;
 }

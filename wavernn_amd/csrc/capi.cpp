@@ -918,7 +918,7 @@ void pack_xcd_slab(const wrnn_ctx &h, std::vector<float> &slab) {
     for (int c = 0; c < kXcdWgs; ++c) {
         float *out = slab.data() + (size_t)c * x.total;
         std::memcpy(out + x.q1a, q1a.data(), (size_t)3 * R * 4);
-        for (int w = 0; w < kXWaves; ++w)
+        for (int w = 0; w < kXWaves; ++w)   // unit pairs (fatchord_xcd.h: GRU2 group g takes pairs 2g, 2g + 1)
             for (int i = 0; i < 2; ++i) {
                 const int u = 2 * w + i, j = c * kXUnits + u;     // unit j, fc row j
                 for (int q = 0; q < 3; ++q)

@@ -8,18 +8,31 @@ namespace wrnn {
 
 constexpr int kXcds = 8;            // XCDs of an MI355X (one row each)
 constexpr int kXcdWgs = 32;         // workgroups (= CUs) per XCD, one per CU
-constexpr int kXWaves = 8;          // compute waves per workgroup (two per SIMD), no loader wave
+constexpr int kXWaves = 8;          // waves per workgroup (two per SIMD), no loader wave
 constexpr int kXThreads = 64 * kXWaves;
-constexpr int kXUnits = 16;         // GRU units per workgroup (R / kXcdWgs), 2 per wave
+constexpr int kXUnits = 16;         // GRU units per workgroup (R / kXcdWgs), 4 per GRU2 wave
 constexpr int kXFcRows = 16;        // fc1 / fc2 rows per workgroup (F / kXcdWgs)
-// wave roles (all eight compute GRU1 and GRU2):
-//   0     samples (polls F2); W_hh1 rows 0..9; W_hh2 rows 24..27 in VGPRs
-//   1, 2  fc1 rows 8h..8h+7 (h = w − 1) from the polled y, weights in VGPRs; W_hh2 LDS rows
-//   3, 4  fc2 rows 8h..8h+7 (h = w − 3) from the polled f1 + their fc3 partials; W_hh1 rows;
-//         wave 4 then gathers a quarter of the next step's GRU1 terms
-//   5..7  W_hh2 rows 8(w − 5)..+7 in VGPRs; W_hh1 rows (5, 7), the h2 gather (6)
+// wave roles (all eight compute GRU1, one unit per thread; waves map to SIMD w mod 4):
+//   0, 5..7  GRU2, one wave per SIMD: wave 0 is group g = 0, wave w ≥ 5 group g = w − 4; engine e
+//            of group g owns units 4g + e (lane 0's gates) and 4g + 2 + e (lane 1's), six W_ih2
+//            gate rows in VGPRs, and publishes y, later h2.  Wave 0 also samples (polls F2) and
+//            has W_hh1 rows 0..9; 5..7: W_hh1 rows (5, 7), the h2 gather (6), the ring (7), one
+//            W_hh2 pass in VGPRs + W_hh2 LDS passes (5, 6)
+//   1, 2     fc1 rows 8h..8h+7 (h = w − 1) from the polled y — polling from barrier B2 on, no
+//            store of their own ahead of the poll; three W_hh2 passes in VGPRs + two from LDS
+//   3, 4     fc2 rows 8h..8h+7 (h = w − 3) from the polled f1 + their fc3 partials; W_hh1 rows
+//            (after wave 0's y store: not issued into GRU2 on the SIMDs shared with waves 7, 0);
+//            three W_hh2 passes in VGPRs (wave 3: + two from LDS); wave 4 gathers a quarter of the
+//            next step's GRU1 terms
+// W_hh2 pass P = rows 2P + e (e = engine).  VGPR passes: wave w = 1..4 holds 3(w − 1)..+2, wave
+// w = 5..7 holds 7 + w; LDS passes 15..23: waves 1, 2 two each (15.., 17..), wave 5 pass 19,
+// wave 6 passes 20, 21, wave 3 passes 22, 23 (wave 7, which also fills the ring, reached the
+// step-end barrier after the sampler with them).
 constexpr int kXWaveFc1 = 1, kXWaveFc2 = 3;
-constexpr int kXH2RegRows = 28;     // W_hh2 rows 0..27 in VGPRs, 28..47 in LDS
+constexpr int kXH2RegRows = 30;     // W_hh2 rows 0..29 in VGPRs, 30..47 in LDS
+constexpr int kXH2LdsRows = 18;
+static_assert(kXH2RegRows == 2 * (4 * 3 + 3 * 1), "W_hh2 VGPR passes: 3 on each fc wave, 1 on waves 5..7");
+static_assert(kXH2RegRows + kXH2LdsRows == 48, "every W_hh2 row of the workgroup has one holder");
 constexpr int kXRing = 4;           // steps of conditioning terms / sampler noise in LDS
 constexpr int kXNoise = 16;         // 11 MoL sampler terms, padded
 
@@ -37,7 +50,7 @@ constexpr long long kXXcdStride = kXHops * kXHopStride + 512;   // granules per 
 
 // Per-workgroup weight slab (floats), all rows natural (512 contiguous):
 struct XcdSlab {
-    int wih2;    // [8 waves][6 rows (2q + i)][512]   W_ih2[:, :R] gate q of unit 2w + i
+    int wih2;    // [8 pairs][6 rows (2q + i)][512]   W_ih2[:, :R] gate q of unit 2p + i (GRU2 group g: pairs 2g, 2g + 1)
     int w1;      // [16][512]                           fc1 rows 16c + r (y part)
     int w2;      // [16][512]                           fc2 rows 16c + r (f1 part)
     int whh2;    // [48][512]   W_hh2 rows u·3 + q (rows < kXH2RegRows in VGPRs, the rest LDS)
@@ -54,7 +67,7 @@ enum XCst { XC_Q2 = 0, XC_BIH1 = 48, XC_BHH1 = 96, XC_BIH2 = 144, XC_BHH2 = 192,
 //   of the own units, b3 (padded to 32)
 
 // Per-workgroup state carried between time chunks (floats):
-// [h1 512 | sg 2048 (terms of the next step) | gh2 48 | h2own 16 | x | pad]
+// [h1 512 | sg 2048 (terms of the next step) | gh2 48 | h2own 16 (by local unit) | x | pad]
 constexpr int kXStateW = 512 + 2048 + 48 + 16 + 16;
 
 struct XcdArgs {
@@ -79,8 +92,8 @@ struct XcdLds {
     int whh1, whh2, h1, h2, sg, w3, f2x, ring, nz, gh2, cst, xs, misc, total;
 };
 
-__host__ __device__ inline XcdLds xcd_lds_layout() {
-    XcdLds l;
+__host__ __device__ constexpr XcdLds xcd_lds_layout() {
+    XcdLds l{};
     int o = 0;
     // the small per-step arrays first (offsets < 64 KiB: lane address + instruction immediate)
     l.h1 = o;    o += 512;
@@ -94,11 +107,12 @@ __host__ __device__ inline XcdLds xcd_lds_layout() {
     l.cst = o;   o += kXCst;
     l.xs = o;    o += 4;                      // x, by step parity
     l.misc = o;  o += 8;                      // [0] abort flag, [1] member index, step flags (step + 1):
-                                              // [2] h2 gathered, [3] (unused), [4] y gathered, [5] f1 gathered
+                                              // [2] h2 gathered, [3] y store issued (wave 0), [4] y gathered, [5] f1 gathered
     l.whh1 = o;  o += 48 * 512;
-    l.whh2 = o;  o += (48 - kXH2RegRows) * 512;
+    l.whh2 = o;  o += kXH2LdsRows * 512;
     l.total = o;
     return l;
 }
+static_assert(xcd_lds_layout().total * 4 <= 160 * 1024, "the XCD kernel's LDS image fits a CU's 160 KB");
 
 }  // namespace wrnn

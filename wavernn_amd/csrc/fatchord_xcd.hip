@@ -10,20 +10,24 @@
 // The 11.4 MB of loop weights fit the XCD's 32 CUs as 96 KB of W_hh1 per CU in LDS and the rest
 // (W_ih2, fc1, fc2 rows, fc3 columns, W_hh2) in the VGPRs of 8 waves (two per SIMD).
 //
-// Workgroup c of an XCD owns GRU units 16c..16c+15 (both GRUs) and fc rows 16c..16c+15; wave w
-// of it units / fc rows 16c + 2w + {0, 1}.  Per step t (x = x_{t-1}):
-//   B1 → GRU1 for ALL units, one per thread, from the gathered terms S (rank-1 in x: no hop)
-//   B2 → W_ih2·h1 for the wave's 6 gate rows (VGPR weights, h1 from LDS) → GRU2 gates → publish
-//        y = x_I + h1 + h2 and h2                                                  [hop Y]
-//   B3 → fc1 rows (2 per wave) → relu → publish f1                               [hop F1]
-//   B4 → fc2 rows → relu → fc3 partial logits of the workgroup's 16 f2 rows → B5 → wave 0 sums
-//        the 8 waves' partials → publish 30 partials                             [hop F2]
+// Workgroup c of an XCD owns GRU units 16c..16c+15 (both GRUs) and fc rows 16c..16c+15.  Every
+// critical role has its own waves (fatchord_xcd.h): GRU2 on waves 0, 5, 6, 7 (one per SIMD, four
+// units each), fc1 on waves 1, 2, fc2 on waves 3, 4, the sampler on wave 0 — so each hop's
+// pollers publish nothing in that hop's window and are already polling when its rows land.
+// Per step t (x = x_{t-1}):
+//   GRU1 for ALL units, one per thread, from the gathered terms S (rank-1 in x: no hop) → B2
+//   waves 0, 5..7: W_ih2·h1 for the wave's 12 gate rows (VGPR weights, h1 from LDS) → GRU2 gates
+//        (lane 0 / 1 of an engine: its two units) → publish y = x_I + h1 + h2       [hop Y]
+//   waves 1, 2 (polling Y from B2 on): fc1 rows (8 per wave) → relu → publish f1  [hop F1]
+//   waves 3, 4: fc2 rows → relu → fc3 partial logits of the workgroup's 16 f2 rows; wave 4 hands
+//        its partials to wave 3 (LDS) → publish 30 partials                        [hop F2]
 //   wave 0 gathers all 32 × 30 partials, sums + b3, samples (MoL, utils/distribution.py:87-123,
-//   redundantly and bit-identically in every workgroup) → x_t.
-// Off the critical path, waves 1..7: W_hh1·h1 (LDS weights) → the GRU1 terms of step t+1 →
-// publish (hop S, double-buffered), gather h2 (wave 6) → W_hh2·h2 (VGPR weights) for the next
-// GRU2, gather S (waves 1, 2, 5 and fc2 wave 4, a quarter each), the conditioning terms and
-// noise of step t+2 into the LDS ring (wave 7).
+//   redundantly and bit-identically in every workgroup) → x_t → step-end barrier.
+// Off the critical path: W_hh1·h1 (LDS weights, waves 0, 3, 4, 5, 7) → the GRU1 terms of step
+// t+1 → publish (hop S, double-buffered); h2 published by the GRU2 waves after "y gathered",
+// gathered by wave 6 → W_hh2·h2 (VGPR rows of waves 1..7 + LDS rows) for the next GRU2; S
+// gathered by waves 1, 2, 5 and fc2 wave 4, a quarter each; the conditioning terms and noise of
+// step t+2 into the LDS ring (wave 7).
 //
 // Membership: each workgroup reads its XCC id from the hardware register and takes an index
 // from a per-XCD arrival counter, so correctness never depends on the dispatcher's placement
@@ -65,13 +69,6 @@ namespace wrnn {
 #ifndef WRNN_XCD_SQ3_WAVE
 #define WRNN_XCD_SQ3_WAVE 4
 #endif
-// y and h2 published per wave: lane 0 stores both engines' units (lanes 0 and 32 before, one in
-// each half of the wave) as one 16-byte pair — 1 row 3.36-3.37 → 3.31-3.33 µs/step,
-// profiles/r05_ab_xcd_pub16.log (the same pairing of the f1 rows / fc3 partials, already adjacent
-// lanes of one store: slower, not kept); 0: per engine (A/B)
-#ifndef WRNN_XCD_PUB16
-#define WRNN_XCD_PUB16 1
-#endif
 #ifndef WRNN_XCD_STAMP_W13
 #define WRNN_XCD_STAMP_W13 5    // stamped builds: the wave whose W_hh2·h2 end is stamp 13 (6: the h2 gatherer)
 #endif
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     float *whh1 = smem + ll.whh1, *whh2l = smem + ll.whh2, *f2x = smem + ll.f2x, *h1s = smem + ll.h1, *h2s = smem + ll.h2, *sg = smem + ll.sg, *w3s = smem + ll.w3;
     float *ring = smem + ll.ring, *nzr = smem + ll.nz, *gh2s = smem + ll.gh2, *cst = smem + ll.cst, *xs = smem + ll.xs;
     int *misc = reinterpret_cast<int *>(smem + ll.misc);
-    int *abort_flag = misc, *h2ready = misc + 2, *f2ready = misc + 3, *ygot = misc + 4, *f1got = misc + 5;
+    int *abort_flag = misc, *h2ready = misc + 2, *ypub = misc + 3, *ygot = misc + 4, *f1got = misc + 5;
 
     // ---- membership: XCD k (row b0 + k) and index c within it
     if (tid == 0) {
@@ -133,42 +130,51 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     const float *S = a.slab + (size_t)c * a.s.total;
     const unsigned long long prow = (unsigned long long)(a.row0 + k);
 
-    // ---- register-resident weights
-    //   wih2 (all waves): GRU2 pass q = gate q of unit ui = 2w + e, chunks li + 32m of the row
-    //   wr (one register set, contents by role):
-    //     waves 1, 2 / 3, 4: fc1 / fc2 rows 8h + r, r = 0..7, at the granules this lane polls (fc8_rows)
-    //     waves 5..7: W_hh2 rows 8(w − 5) + 2p + e, p = 0..3, at wr[4p + m] (32-lane chunks)
-    //     wave 0: wr[0..7] the F2 poll buffer, wr[8..15] W_hh2 rows 24 + 2p + e, p = 0..1
-    f4v wih2[3][4], wr[16];
+    // ---- register-resident weights: one role-indexed set of 28 float4 (chunks li + 32m of a row)
+    //   GRU2 waves (0, 5..7; group g2): W[12j + 4q + m] = W_ih2 gate q of unit 4·g2 + 2j + e (slab
+    //     pair 2·g2 + j); W[24 + m]: W_hh2 pass 7 + w (waves 5..7; wave 0: none — its F2 poll buffer
+    //     is a transient of the poll, when no GRU2 operand is live)
+    //   waves 1, 2 / 3, 4: W[0..15] fc1 / fc2 rows 8h + r, r = 0..7, at the granules this lane polls
+    //     (fc8_rows); W[16 + 4p + m]: W_hh2 passes 3(w − 1) + p, p = 0..2
+    f4v W[28];
     auto ldrow = [&](const float *row, int m) { return *reinterpret_cast<const f4v *>(row + 4 * (li + 32 * m)); };
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) wih2[q][m] = ldrow(S + a.s.wih2 + (wave * 6 + 2 * q + eng) * R, m);
     const bool fcw = wave >= kXWaveFc1 && wave < kXWaveFc2 + 2;
+    const bool g2w = !fcw;
+    const int g2 = g2w && wave != 0 ? wave - 4 : 0;  // GRU2 group (GRU2 waves)
     if (fcw) {
         const int hf = (wave - kXWaveFc1) & 1;
-        const float *W = S + (wave < kXWaveFc2 ? a.s.w1 : a.s.w2) + hf * 8 * R;
+        const float *Wf = S + (wave < kXWaveFc2 ? a.s.w1 : a.s.w2) + hf * 8 * R;
 #pragma unroll
         for (int r = 0; r < 8; ++r)
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
-                const f2v lo = *reinterpret_cast<const f2v *>(W + r * R + 2 * (lane + 64 * (2 * hh)));
-                const f2v hi = *reinterpret_cast<const f2v *>(W + r * R + 2 * (lane + 64 * (2 * hh + 1)));
-                wr[2 * r + hh] = f4v{lo.x, lo.y, hi.x, hi.y};
+                const f2v lo = *reinterpret_cast<const f2v *>(Wf + r * R + 2 * (lane + 64 * (2 * hh)));
+                const f2v hi = *reinterpret_cast<const f2v *>(Wf + r * R + 2 * (lane + 64 * (2 * hh + 1)));
+                W[2 * r + hh] = f4v{lo.x, lo.y, hi.x, hi.y};
             }
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int m = 0; m < 4; ++m) W[16 + 4 * p + m] = ldrow(S + a.s.whh2 + (2 * (3 * (wave - 1) + p) + eng) * R, m);
     } else {
-        const int rb = wave == 0 ? 24 - 4 : 8 * (wave - 5);   // wave 0: passes 2, 3 → rows 24..27
 #pragma unroll
-        for (int p = 0; p < 4; ++p)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int m = 0; m < 4; ++m)
-                wr[4 * p + m] = (wave != 0 || p >= 2) ? ldrow(S + a.s.whh2 + (rb + 2 * p + eng) * R, m)
-                                                      : f4v{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    W[12 * j + 4 * q + m] = ldrow(S + a.s.wih2 + ((2 * g2 + j) * 6 + 2 * q + eng) * R, m);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            W[24 + m] = wave != 0 ? ldrow(S + a.s.whh2 + (2 * (7 + wave) + eng) * R, m) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
     }
+    auto W4 = [&](int i) -> const f4v(&)[4] { return *reinterpret_cast<const f4v(*)[4]>(&W[i]); };
+    auto W4x16 = [&]() -> const f4v(&)[16] { return *reinterpret_cast<const f4v(*)[16]>(&W[0]); };
     // GRU1 of unit tid: x-coefficients
     const float q1r = S[a.s.q1a + tid], q1z = S[a.s.q1a + R + tid], q1n = S[a.s.q1a + 2 * R + tid];
-    const int ui = wave * 2 + eng;                   // this engine's local GRU unit
+    // GRU2 waves: the local GRU2 unit whose gates this lane forms (lane 0 / 1 of an engine: its
+    // first / second unit; the other lanes compute along, their results are not used)
+    const int ui = 4 * g2 + 2 * (li & 1) + eng;
     // W_hh1 rows (waves 0, 3, 4, 5: ten each, wave 7: eight): gh0 + 2p + e, p = 0..4; lane li < 5
     // of an engine publishes the terms of its row gh0 + 2·li + e
     const bool gh1w = wave == 0 || wave == 3 || wave == 4 || wave == 5 || wave == 7;
@@ -232,6 +238,18 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
         const int rr = rb + 2 * li + eng;
         if (li < np) gh2s[rr] = li == 0 ? gh[0] : li == 1 ? gh[1] : li == 2 ? gh[2] : li == 3 ? gh[3] : gh[4];
     };
+    // W_hh2 LDS passes p0 .. p0 + np − 1 (np ≤ 2; pass P = rows 2P + e, LDS row 2P + e − kXH2RegRows)
+    auto gh2_lds = [&](int p0, int np, const f4v (&hx)[4]) {
+        float gh[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            if (p < np) {
+                f4v w4[4];
+                e32x(whh2l + (2 * (p0 + p) + eng - kXH2RegRows) * R, li, w4);
+                gh[p] = e32dot(w4, hx);
+            }
+        gh2_store(2 * p0, np, gh);
+    };
     // a quarter of step t's GRU1 terms (waves 1, 2, 5, WRNN_XCD_SQ3_WAVE: 512 granules each, one
     // poll round)
     auto gather_terms = [&](int t) {
@@ -242,6 +260,16 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
                      });
     };
 
+    // a GRU2 wave's four granules of a hop (units 4·g2 .. 4·g2 + 3; unit 4·g2 + 2j + e lives in lane
+    // j of engine e): lanes 0 and 1 store the pairs (lane j, lane 32 + j) as one 16-byte store each,
+    // one instruction, 32 contiguous bytes
+    auto pub4 = [&](int hop, float v, uint32_t tag) {
+        const uint32_t e1a = __builtin_amdgcn_readlane(__float_as_uint(v), 32);
+        const uint32_t e1b = __builtin_amdgcn_readlane(__float_as_uint(v), 33);
+        if (lane < 2)
+            __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(v), tag, lane == 0 ? e1a : e1b, tag}, xgr,
+                                                   (XGI(hop) + c * kXUnits + 4 * g2 + 2 * lane) * 8, 0, 0);
+    };
     // ---- prologue: W_hh1, fc3 columns, small vectors, ring slots t0..t0+2, state
     {
         const f4v *src = reinterpret_cast<const f4v *>(S + a.s.whh1);
@@ -249,7 +277,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
         for (int i = tid; i < 48 * R / 4; i += kXThreads) dst[i] = src[i];
         src = reinterpret_cast<const f4v *>(S + a.s.whh2 + kXH2RegRows * R);
         dst = reinterpret_cast<f4v *>(whh2l);
-        for (int i = tid; i < (48 - kXH2RegRows) * R / 4; i += kXThreads) dst[i] = src[i];
+        for (int i = tid; i < kXH2LdsRows * R / 4; i += kXThreads) dst[i] = src[i];
         for (int i = tid; i < kXFcRows * 32; i += kXThreads) w3s[i] = S[a.s.w3 + i];
         for (int i = tid; i < kXCst; i += kXThreads) cst[i] = S[a.s.cst + i];
         for (int t = a.t0; t < a.t0 + 3; ++t) {
@@ -261,7 +289,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     const bool resume = a.t0 > 0;
     float *st = a.state + ((size_t)k * kXcdWgs + c) * kXStateW;
     float h1v = resume ? st[tid] : 0.0f;              // h1 of unit tid (recurrent, this thread)
-    float h2own = resume ? st[512 + 2048 + 48 + ui] : 0.0f;   // h2 of this engine's unit
+    float h2own = resume ? st[512 + 2048 + 48 + ui] : 0.0f;   // h2 of this lane's GRU2 unit (GRU2 waves)
     // consume the carried-state loads here (an empty asm use: the wait lands before the loop);
     // left pending into the loop, their first use inside it is an s_waitcnt vmcnt(0) in EVERY
     // step (GRU1's h1 update), draining all the wave's in-flight publishes and loads there
@@ -298,8 +326,10 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
         XSTAMP(0);
         if (kDbg && a.dbg && wave == 0 && lane == 0 && t - a.t0 < a.dbg_steps)   // shader clock beside the 100 MHz one
             a.dbg[((size_t)mem * a.dbg_steps + (t - a.t0)) * kStamps + 15] = (unsigned)__builtin_amdgcn_s_memtime();
-        // operands of the GRU2 gate math (engine unit ui): LDS reads issued before GRU1's
-        // transcendental chain (behind its h1 store the compiler could not move them)
+        // operands of the GRU2 gate math (this lane's unit ui): LDS reads issued before GRU1's
+        // transcendental chain (behind its h1 store the compiler could not move them).  Every wave
+        // issues them (the fc waves read units 0..3 and drop the values): under a role branch their
+        // waits land at the branch's join, ahead of GRU1, and barrier B2 comes 0.04 µs later
         float q2v[3], p2v[3], bi2[3], ghv[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -323,53 +353,49 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
         const float xi = fmaf(wi0v, x, civ);   // x_I of unit ui
         bar();
         XSTAMP(1);
-        // ---- GRU2 (:212-214): pass q → gate q of unit ui (W_ih2[:, :R]·h1), all lanes of the engine
-        {
+        // ---- GRU2 (:212-214) on waves 0, 5..7: the engine's two units, W_ih2[:, :R]·h1 of their six
+        // gate rows as two 3-row reduce-scatters (each row's sum tree as e32dot's); both leave their
+        // gates in every lane of quad 0, lane 0 takes the first unit's, lane 1 the second's, and one
+        // pass of gate math serves both
+        if (g2w) {
             f4v hx[4];
             e32x(h1s, li, hx);
-            // x_I + h1 of the engine's unit (:212) formed before the dots and pinned there: hipcc
-            // otherwise sinks the h1 LDS read into the publishing lane's branch after the gate math
+            // x_I + h1 of the lane's unit (:212) formed before the dots and pinned there: hipcc
+            // otherwise sinks the h1 LDS read into the publishing lanes' branch after the gate math
             float yb = xi + h1s[c * kXUnits + ui];
             asm volatile("" : "+v"(yb));
-            float g_r, g_z, g_n;   // valid in lanes li == 0 (the publishing lane)
+            float a_r, a_z, a_n, b_r, b_z, b_n;
             if (WRNN_XCD_RS) {
-                e32dot3_rs(wih2[0], wih2[1], wih2[2], hx, lane, g_r, g_z, g_n);
+                e32dot3_rs(W4(0), W4(4), W4(8), hx, lane, a_r, a_z, a_n);
+                e32dot3_rs(W4(12), W4(16), W4(20), hx, lane, b_r, b_z, b_n);
+                b_r = WRNN_DPP(b_r, 0x00);   // quad_perm [0,0,0,0]: e32dot3_rs leaves r in lane 0 only
             } else {
-                g_r = e32dot(wih2[0], hx);
-                g_z = e32dot(wih2[1], hx);
-                g_n = e32dot(wih2[2], hx);
+                a_r = e32dot(W4(0), hx);
+                a_z = e32dot(W4(4), hx);
+                a_n = e32dot(W4(8), hx);
+                b_r = e32dot(W4(12), hx);
+                b_z = e32dot(W4(16), hx);
+                b_n = e32dot(W4(20), hx);
             }
+            const bool second = (li & 1) != 0;
+            const float g_r = second ? b_r : a_r, g_z = second ? b_z : a_z, g_n = second ? b_n : a_n;
             const float hn = gru_gate_math(g_r + p2q[0], g_z + p2q[1], g_n + p2q[2], ghv[0], ghv[1], ghv[2], h2own);
             h2own = hn;
-            // y = (x_I + h1) + h2 (:212, :216)
-            const float y = yb + hn;
-            if (WRNN_XCD_PUB16) {   // both engines' granules (units 2w, 2w + 1) in one 16-byte store
-                const float y1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(y), 32));
-                if (lane == 0)
-                    __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(y), tag, __float_as_uint(y1), tag}, xgr,
-                                                           (XGI(XH_Y) + c * kXUnits + 2 * wave) * 8, 0, 0);
-            } else if (li == 0) {
-                xpub_b(xgr, XGI(XH_Y) + c * kXUnits + ui, tag, y);   // h2: after hop Y (pub_h2)
-            }
+            // y = (x_I + h1) + h2 (:212, :216); h2: after hop Y (pub_h2)
+            pub4(XH_Y, yb + hn, tag);
+            if (wave == 0) set_flag(ypub, tag);
         }
         XSTAMP(2);
         // Off-critical memory traffic (GRU1-term and h2 publishes, the S / h2 gathers, the ring)
         // waits for the critical waves' flags: hop Y's window (GRU2 → y gathered) carries only y,
         // hop F1's only f1, hop F2's only the partials (a second poll stream or a burst of stores
         // beside a critical poll costs it ≈ 0.2 µs: tools/xcdhop.hip PACED variants).
-        //   after y gathered  : publish the GRU1 terms of step t+1 and h2
-        //   after f1 gathered : gather h2 (wave 6), S (waves 1, 2, 5, 6), the ring (wave 7)
-        //   after h2 gathered : W_hh2·h2 (waves 0, 1, 2, 5, 6, 7)
-        auto pub_h2 = [&]() {
-            if (WRNN_XCD_PUB16) {
-                const float h1o = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(h2own), 32));
-                if (lane == 0)
-                    __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(h2own), tag, __float_as_uint(h1o), tag},
-                                                           xgr, (XGI(XH_H2) + c * kXUnits + 2 * wave) * 8, 0, 0);
-            } else if (li == 0) {
-                xpub_b(xgr, XGI(XH_H2) + c * kXUnits + ui, tag, h2own);
-            }
-        };
+        //   after wave 0's y store : W_hh1·h1 on the fc2 waves (not into GRU2's issue slots on the
+        //                            SIMDs they share with waves 7 and 0)
+        //   after y gathered  : publish the GRU1 terms of step t+1 and h2 (waves 0, 5..7)
+        //   after f1 gathered : gather h2 (wave 6), S (waves 1, 2, 5, then 4), the ring (wave 7)
+        //   after h2 gathered : W_hh2·h2 (waves 1..7)
+        auto pub_h2 = [&]() { pub4(XH_H2, h2own, tag); };   // GRU2 waves
         // fc waves: lane l ends fc8_rows with row 8h + j + 2·(l >> 4) in o[j]; lanes with
         // (l & 15) < 2 publish row 8h + (l & 1) + 2·(l >> 4)
         const int jq = lane & 1, rho = jq + 2 * (lane >> 4);
@@ -380,12 +406,6 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
                 wait_flag(ygot, tag);
                 publish_terms(t + 1, gh);
                 pub_h2();
-                wait_flag(h2ready, tag);
-                f4v hx[4];
-                e32x(h2s, li, hx);
-                float g2[5] = {e32dot(*reinterpret_cast<const f4v(*)[4]>(&wr[8]), hx),
-                               e32dot(*reinterpret_cast<const f4v(*)[4]>(&wr[12]), hx), 0.0f, 0.0f, 0.0f};
-                gh2_store(24, 2, g2);
             }
             // ---- hop F2: Σ of the 32 workgroups' partials + b3 → sample
             // lane l: logits (2jp, 2jp+1), jp = l & 15, of producers 8·(l >> 4) + m, m = 0..7:
@@ -398,9 +418,9 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
             const int goff = pg * 8 * kXF2Line * 8 + jp * 16;
             const unsigned long long c0 = __builtin_amdgcn_s_memrealtime();
             unsigned spins = 0;
-            // the polled pieces live in wr[0..7] (wave 0 holds no weights there), polled in place
-            // and read after the loop (the abort path zeroes them there: no copies on the exit)
-            u4v *v = reinterpret_cast<u4v *>(&wr[0]);
+            // the polled pieces: a transient of the poll (no GRU2 operand is live here), polled in
+            // place and read after the loop (the abort path zeroes them there: no copies on the exit)
+            u4v v[8];
             for (;;) {
 #pragma unroll
                 for (int m = 0; m < 8; ++m) v[m] = ld16_sc1(rf, goff + m * kXF2Line * 8);
@@ -456,12 +476,11 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) yk[kk] = f2v{__uint_as_float(v[kk].x), __uint_as_float(v[kk].z)};
             float o[2];
-            fc8_rows(wr, yk, o);
+            fc8_rows(W4x16(), yk, o);
             const float A = (jq == 0 ? o[0] : o[1]) + v1;
             if ((lane & 15) < 2) xpub_b(xgr, XGI(XH_F1) + c * kXFcRows + rg, tag, A > 0.0f ? A : 0.0f);
             XSTAMPW(4, 1);
-            if (more && !WRNN_XCD_SKIP_RECUR) {   // h2 out; after f1 gathered: a quarter of the next S; W_hh2 LDS rows 28 + 10h + 2p + e
-                pub_h2();
+            if (more && !WRNN_XCD_SKIP_RECUR) {   // after f1 gathered: a quarter of the next S; W_hh2 VGPR passes 3h.., LDS passes 15 + 2h..
                 wait_flag(f1got, tag);
                 if (!WRNN_XCD_SKIP_SG) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -470,24 +489,19 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
                 wait_flag(h2ready, tag);
                 f4v hx[4];
                 e32x(h2s, li, hx);
-                float gh[5];
-#pragma unroll
-                for (int p = 0; p < 5; ++p) {
-                    f4v w4[4];
-                    e32x(whh2l + (10 * hf + 2 * p + eng) * R, li, w4);
-                    gh[p] = e32dot(w4, hx);
-                }
-                gh2_store(kXH2RegRows + 10 * hf, 5, gh);
+                const float gh[5] = {e32dot(W4(16), hx), e32dot(W4(20), hx), e32dot(W4(24), hx), 0.0f, 0.0f};
+                gh2_store(6 * hf, 3, gh);
+                gh2_lds(15 + 2 * hf, 2, hx);
                 XSTAMPW(11, 1);
             }
         } else if (wave < kXWaveFc2 + 2) {
             const int hf = wave - kXWaveFc2;
-            if (more && !WRNN_XCD_SKIP_RECUR) {   // W_hh1 rows; after y gathered their terms and h2 out
+            if (more && !WRNN_XCD_SKIP_RECUR) {   // W_hh1 rows once GRU2 is through; after y gathered their terms out
+                wait_flag(ypub, tag);
                 float gh[5];
                 gh1_dots(gh);
                 wait_flag(ygot, tag);
                 publish_terms(t + 1, gh);
-                pub_h2();
             }
             XSTAMPW(9, 3);
             // ---- hop F1 → fc2 (:220-221) rows 8h.. in registers → relu → fc3 partial logits of
@@ -507,7 +521,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) fk[kk] = f2v{__uint_as_float(v[kk].x), __uint_as_float(v[kk].z)};
             float o[2];
-            fc8_rows(wr, fk, o);
+            fc8_rows(W4x16(), fk, o);
             float p = 0.0f;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -546,10 +560,19 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 gather_terms(t + 1);
             }
+            if (more && !WRNN_XCD_SKIP_RECUR) {   // W_hh2 VGPR passes 6 + 3h..; wave 3: LDS passes 22, 23
+                wait_flag(h2ready, tag);
+                f4v hx[4];
+                e32x(h2s, li, hx);
+                const float gh[5] = {e32dot(W4(16), hx), e32dot(W4(20), hx), e32dot(W4(24), hx), 0.0f, 0.0f};
+                gh2_store(12 + 6 * hf, 3, gh);
+                if (hf == 0) gh2_lds(22, 2, hx);
+            }
         } else if (more) {
             // ---- waves 5..7: W_hh1 rows (5, 7) → after y gathered their terms and h2 out; after
             // f1 gathered: h2 (wave 6, then flag), an S quarter (5; 6 with WRNN_XCD_SQ3_WAVE 6),
-            // the ring (7); after h2 gathered: W_hh2·h2 (VGPR rows)
+            // the ring (7); after h2 gathered: W_hh2·h2 (VGPR pass 7 + w; LDS pass 19 on wave 5,
+            // 20, 21 on wave 6)
             if (WRNN_XCD_SKIP_RECUR) {
                 if (wave == 7) {
                     wait_flag(f1got, tag);
@@ -590,7 +613,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
             } else if (t + 2 >= a.t0 + 3) {
                 // ring: step t+2's terms and sampler noise, loaded and stored within this window
                 // (a load carried across steps in registers would not fit the VGPR budget, and an
-                // LDS-DMA makes hipcc wait for it before every later LDS access of the issuing wave)
+                // LDS-DMA makes hipcc wait for it before every later LDS access of the issuing wave;
+                // issued here and stored after the wave's W_hh2 pass: 3.25 -> 3.30 us/step)
                 if (t + 2 <= t_terms && lane < kXTerms / 4)
                     reinterpret_cast<f4v *>(RING(t + 2))[lane] = reinterpret_cast<const f4v *>(TERMS(t + 2))[lane];
                 if (t + 2 < a.L && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
@@ -600,11 +624,9 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
             {
                 f4v hx[4];
                 e32x(h2s, li, hx);
-                float gh[5];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) gh[p] = e32dot(*reinterpret_cast<const f4v(*)[4]>(&wr[4 * p]), hx);
-                gh[4] = 0.0f;
-                gh2_store(8 * (wave - 5), 4, gh);
+                const float gh[5] = {e32dot(W4(24), hx), 0.0f, 0.0f, 0.0f, 0.0f};
+                gh2_store(2 * (7 + wave), 1, gh);
+                if (wave != 7) gh2_lds(wave == 5 ? 19 : 20, wave == 5 ? 1 : 2, hx);
                 XSTAMPW(13, WRNN_XCD_STAMP_W13);
             }
         }
@@ -623,7 +645,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     st[tid] = h1v;
     for (int i = tid; i < 4 * R; i += kXThreads) st[512 + i] = sg[i];
     if (tid < 48) st[512 + 2048 + tid] = gh2s[tid];
-    if (li == 0) st[512 + 2048 + 48 + ui] = h2own;
+    if (g2w && li < 2) st[512 + 2048 + 48 + ui] = h2own;
     if (tid == 0) st[512 + 2048 + 48 + 16] = xs[(t_end - 1) & 1];
 }
 
