@@ -384,6 +384,11 @@ def cases():
         "gen_raw_batched_mulaw": ("gen", dict(d=R, T=30, batched=True, target=2000, overlap=200, mu_law=True)),
         "gen_mol_batched": ("gen", dict(d=M, T=30, batched=True, target=1500, overlap=300, mu_law=True)),
         "gen_raw_tiny_unbatched": ("gen", dict(d=syn.TINY_RAW, T=24, batched=False, target=1000, overlap=100, mu_law=False)),
+        # an odd upsample geometry (two stages, hop 12 < 32, feat 30, pad 3), fold-batched with a
+        # padded tail fold: pins oracle.upsample and the oracle loop away from (5, 5, 11)
+        "gen_mol_hop12": ("gen", dict(d=syn.FatchordDims(feat_dims=30, upsample_factors=(3, 4), hop_length=12,
+                                                         pad=3, compute_dims=16, res_blocks=1),
+                                      T=60, batched=True, target=150, overlap=20, mu_law=True, cond_stride=5)),
         # BASELINE sizes through the whole generate() (VERDICT r04 "do this" 1): config 1
         # exactly (RAW 9-bit, 1 s, unbatched), config 2 unbatched (the headline) and in the
         # reference's default fold-batched mode (hparams.py:58-60), config 3 (60 s, 115 folds)

@@ -40,11 +40,18 @@ def _oracle_mel_up(mel, taps, scales, pad):
     return m[:, pad * total:-pad * total].T
 
 
-@pytest.mark.parametrize("case", ["box", "random", "small"])
+@pytest.mark.parametrize("case", ["box", "random", "small", "boundary3", "boundary7"])
 def test_frame_weights_reproduce_the_cascade(case):
+    """boundary3 / boundary7: pad·hop exactly the cascade's reach E = Σ s_i·hop/(s_1…s_i), the edge
+    of the exactness claim — (4,) pad 1: E = 4 = 1·4, frames f − 1 … f + 1; (1, 1, 2) pad 3:
+    E = 2 + 2 + 2 = 6 = 3·2, frames f − 3 … f + 3."""
     rng = np.random.default_rng(7)
     if case == "small":
         scales, pad = (2, 3), 2
+    elif case == "boundary3":
+        scales, pad = (4,), 1
+    elif case == "boundary7":
+        scales, pad = (1, 1, 2), 3
     else:
         scales, pad = (5, 5, 11), 2
     if case == "box":
@@ -56,9 +63,12 @@ def test_frame_weights_reproduce_the_cascade(case):
     jlo, nJ, coef = condition.frame_weights(spec)
     hop = int(np.prod(scales))
     assert coef.shape == (hop, nJ) and nJ <= 8
+    if case.startswith("boundary"):
+        assert (jlo, nJ) == {"boundary3": (-1, 3), "boundary7": (-3, 7)}[case]
     mel = rng.standard_normal((80, 9)).astype(np.float32)
     want = _oracle_mel_up(mel, taps, scales, pad)
     got = _mel_up_frames(mel, jlo, coef, hop)
+    print(f"{case}: jlo {jlo} nJ {nJ} max |Δ| {np.abs(got - want).max():.3g} of {np.abs(want).max():.3g}")
     # coef rounded to fp32 (relative 6e-8 each); the stage-wise cascade in float64
     np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6 * np.abs(want).max())
 
@@ -81,3 +91,14 @@ def test_short_pad_has_no_exact_frame_form():
     taps = [np.full(2 * s + 1, 1.0 / (2 * s + 1), np.float32) for s in (5, 5, 11)]
     with pytest.raises(nat.WrnnError):
         condition.frame_weights(condition.UpsampleSpec(80, 128, 1, (5, 5, 11), taps))
+
+
+def test_more_than_eight_frames_have_no_frame_form():
+    """(1, 1, 1, 2), pad 4: the pad covers the reach (E = 8 = 4·2) but the response spans frames
+    f − 4 … f + 4, nJ = 9 > the 8 rows the interpolation kernel keeps in registers."""
+    taps = [np.full(2 * s + 1, 1.0 / (2 * s + 1), np.float32) for s in (1, 1, 1, 2)]
+    with pytest.raises(nat.WrnnError):
+        condition.frame_weights(condition.UpsampleSpec(80, 128, 4, (1, 1, 1, 2), taps))
+    # one stage fewer is supported at the same hop: the refusal is nJ's, not the pad's
+    jlo, nJ, _ = condition.frame_weights(condition.UpsampleSpec(80, 128, 4, (1, 1, 2), taps[1:]))
+    assert (jlo, nJ) == (-3, 7)

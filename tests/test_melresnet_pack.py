@@ -1,9 +1,12 @@
 """The fused MelResNet's packed weights (condition.melresnet_pack, every BatchNorm folded into its
-conv) interpreted on the CPU exactly as csrc/melresnet.hip walks them, against the reference-layout
-torch module in eval mode (fatchord_version.py:13-48).  The kernel itself: tests/test_gpu_melresnet.py."""
+conv) interpreted on the CPU exactly as csrc/melresnet.hip walks them (tests/melresnet_ref.py),
+against the reference-layout torch module in eval mode (fatchord_version.py:13-48).  The kernel
+itself: tests/test_gpu_melresnet.py, tests/test_gpu_melresnet_shapes.py."""
 import numpy as np
 import pytest
 import torch
+
+from tests import melresnet_ref as mr
 
 from wavernn_amd import condition
 from wavernn_amd import synthetic as syn
@@ -17,43 +20,37 @@ def _module(d, seed):
     return m.upsample.resnet.eval()
 
 
-def _run_packed(p, cfg, x):
-    """x [U][in][T + 2pad] float64 → [U][R][T], the kernel's layer order and layouts."""
-    cin, C, R, K = cfg.in_dims, cfg.compute_dims, cfg.res_out_dims, 2 * cfg.pad + 1
-    U, _, Tp = x.shape
-    T = Tp - K + 1
-    o = 0
-
-    def take(n):
-        nonlocal o
-        v = p[o:o + n]
-        o += n
-        return v
-    W0, b0 = take(cin * K * C).reshape(cin * K, C), take(C)
-    cols = np.stack([x[:, c, tap:tap + T] for c in range(cin) for tap in range(K)], 1)   # [U][cin·K][T]
-    a = np.maximum(np.einsum("kc,ukt->uct", W0, cols) + b0[None, :, None], 0.0)
-    for _ in range(cfg.res_blocks):
-        W1, b1, W2, b2 = take(C * C).reshape(C, C), take(C), take(C * C).reshape(C, C), take(C)
-        h = np.maximum(np.einsum("kc,ukt->uct", W1, a) + b1[None, :, None], 0.0)
-        a = a + np.einsum("kc,ukt->uct", W2, h) + b2[None, :, None]
-    Wo, bo = take(C * R).reshape(C, R), take(R)
-    assert o == p.size
-    return np.einsum("kr,ukt->urt", Wo, a) + bo[None, :, None]
-
-
 @pytest.mark.parametrize("d", [syn.DEFAULT_MOL, syn.TINY_MOL])
 def test_packed_weights_reproduce_the_module(d):
     res = _module(d, 3)
     # non-trivial running statistics (the synthetic state's are the defaults)
     g = torch.Generator().manual_seed(5)
-    for mod in res.modules():
-        if isinstance(mod, torch.nn.BatchNorm1d):
-            mod.running_mean.copy_(torch.randn(mod.num_features, generator=g) * 0.1)
-            mod.running_var.copy_(torch.rand(mod.num_features, generator=g) + 0.5)
+    mr.randomize_bn(res, g)
     cfg = condition.melresnet_cfg(res)
     packed = condition.melresnet_pack(res).numpy().astype(np.float64)
     x = torch.rand(2, d.feat_dims, 23 + 2 * d.pad, generator=g)
     with torch.no_grad():
         want = res(x).double().numpy()
-    got = _run_packed(packed, cfg, x.double().numpy())
+    got = mr.run_packed(packed, cfg, x.double().numpy())
     np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5 * np.abs(want).max())
+
+
+def test_packed_weights_reproduce_an_odd_geometry():
+    """in 30, pad 3 (K = 7), C 30, R 18, 2 blocks (the GPU tests' scalar-staging geometry) from the
+    shared builder: the float64 module (no fp32 rounding but the packed weights') against the
+    interpreter, and the builder's promise of a channel that ReLU kills."""
+    res = mr.build(2, 30, 30, 18, 3, seed=1)
+    g = torch.Generator().manual_seed(6)
+    x = torch.rand(2, 30, 23 + 2 * 3, generator=g)
+    assert 1 in mr.dead_channels(res, x)
+    cfg, packed, got = mr.reference(res, x)
+    assert (cfg.in_dims, cfg.compute_dims, cfg.res_out_dims, cfg.res_blocks, cfg.pad) == (30, 30, 18, 2, 3)
+    assert packed.numel() == 30 * 7 * 30 + 30 + 2 * 2 * (30 * 30 + 30) + 30 * 18 + 18
+    with torch.no_grad():
+        want32 = res(x).double().numpy()
+        want64 = res.double()(x.double()).numpy()
+    err32, err64 = np.abs(got - want32).max(), np.abs(got - want64).max()
+    print(f"max |Δ| vs fp32 module {err32:.3g}, vs float64 module {err64:.3g} of {np.abs(want64).max():.3g}")
+    np.testing.assert_allclose(got, want32, rtol=1e-5, atol=1e-5 * np.abs(want32).max())
+    # against the module in float64 only the packed weights' fp32 rounding is left
+    assert err64 <= 1e-5 * np.abs(want64).max()

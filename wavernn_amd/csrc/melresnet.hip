@@ -171,25 +171,50 @@ int mr_num_cus() {
     return cus[dev];
 }
 
-// The tile form for U utterances of T frames: 16-frame tiles, or 4-frame tiles when the 16-frame
-// grid has fewer workgroups than the device has CUs (WRNN_MR_FRAMES=16|4 forces one).  Sets the
-// frames-per-thread of the compute / output layers; false when the channel counts fit neither.
-bool mr_choose(const wrnn_melresnet_cfg *cfg, int U, int T, int *F_, int *fc_, int *fr_, size_t *lds_) {
+// The compiled forms (tile frames, frames per thread of the compute layers, of the output layer):
+// the ONE list both mr_choose and the launch read, so the query and the launch cannot disagree.
+// 16-frame tiles with C = 256 (fc = 16) are not listed: 2·256·16 + 128·256 floats of activations and
+// staged weights are exactly the 160 KiB of LDS before the mel tile, so no configuration fits.
+#define WRNN_MR_FORMS(X)                                                                          \
+    X(16, 8, 8) X(16, 1, 1) X(16, 2, 2) X(16, 4, 4) X(16, 8, 1) X(16, 8, 2) X(16, 8, 4) X(16, 8, 16) \
+    X(16, 1, 8) X(16, 2, 8) X(16, 4, 8)                                                           \
+    X(4, 2, 2) X(4, 1, 1) X(4, 4, 4) X(4, 2, 1) X(4, 1, 2) X(4, 4, 2) X(4, 2, 4) X(4, 4, 1) X(4, 1, 4)
+
+bool mr_compiled(int F, int fc, int fr) {
+#define WRNN_MR_HAS(FF, A, B) \
+    if (F == FF && fc == A && fr == B) return true;
+    WRNN_MR_FORMS(WRNN_MR_HAS)
+#undef WRNN_MR_HAS
+    return false;
+}
+
+// Whether the F-frame form runs these dims: a thread layout for both channel counts, a compiled
+// kernel for the pair, and the tile within the LDS
+bool mr_form(const wrnn_melresnet_cfg *cfg, int F, int *fc_, int *fr_, size_t *lds_) {
     using namespace wrnn;
     const int K = 2 * cfg->pad + 1;
+    *fc_ = mr_fpt(cfg->compute_dims, F), *fr_ = mr_fpt(cfg->res_out_dims, F);
+    *lds_ = ((size_t)cfg->in_dims * (F + K - 1) + 2 * (size_t)cfg->compute_dims * F +
+             (size_t)kMrKc * std::max(cfg->compute_dims, cfg->res_out_dims)) * 4;
+    return *fc_ && *fr_ && mr_compiled(F, *fc_, *fr_) && *lds_ <= 160 * 1024;
+}
+
+// The tile form for U utterances of T frames: 16-frame tiles, or 4-frame tiles when the 16-frame
+// grid has fewer workgroups than the device has CUs (WRNN_MR_FRAMES=16|4 asks for one).  Dims that
+// only the other form runs take the other form, whichever was preferred: support depends on the
+// channel counts alone, never on U·T.  Sets the frames-per-thread of the compute / output layers;
+// false when neither form runs the dims.
+bool mr_choose(const wrnn_melresnet_cfg *cfg, int U, int T, int *F_, int *fc_, int *fr_, size_t *lds_) {
+    using namespace wrnn;
     const char *fe = std::getenv("WRNN_MR_FRAMES");
     int F = (long long)U * ((T + kMrFBig - 1) / kMrFBig) >= mr_num_cus() ? kMrFBig : kMrFSmall;
     if (fe && (std::atoi(fe) == kMrFBig || std::atoi(fe) == kMrFSmall)) F = std::atoi(fe);
-    int fc = mr_fpt(cfg->compute_dims, F), fr = mr_fpt(cfg->res_out_dims, F);
-    if ((!fc || !fr) && F == kMrFSmall) {   // channel counts only the 16-frame form covers
-        F = kMrFBig;
-        fc = mr_fpt(cfg->compute_dims, F);
-        fr = mr_fpt(cfg->res_out_dims, F);
+    if (!mr_form(cfg, F, fc_, fr_, lds_)) {
+        F = F == kMrFBig ? kMrFSmall : kMrFBig;
+        if (!mr_form(cfg, F, fc_, fr_, lds_)) return false;
     }
-    const size_t lds = ((size_t)cfg->in_dims * (F + K - 1) + 2 * (size_t)cfg->compute_dims * F +
-                        (size_t)kMrKc * std::max(cfg->compute_dims, cfg->res_out_dims)) * 4;
-    *F_ = F, *fc_ = fc, *fr_ = fr, *lds_ = lds;
-    return fc && fr && lds <= 160 * 1024;
+    *F_ = F;
+    return true;
 }
 }  // namespace
 
@@ -220,13 +245,7 @@ int wrnn_melresnet(const wrnn_melresnet_cfg *cfg, const float *packed, const flo
         hipLaunchKernelGGL((melresnet_kernel<FF, A, B>), grid, dim3(kMrThreads), lds, st, a);       \
         return hipGetLastError() == hipSuccess ? WRNN_OK : WRNN_EHIP;                              \
     }
-    WRNN_MR_CASE(16, 8, 8) WRNN_MR_CASE(16, 1, 1) WRNN_MR_CASE(16, 2, 2) WRNN_MR_CASE(16, 4, 4)
-    WRNN_MR_CASE(16, 16, 16) WRNN_MR_CASE(16, 8, 1) WRNN_MR_CASE(16, 8, 2) WRNN_MR_CASE(16, 8, 4)
-    WRNN_MR_CASE(16, 8, 16) WRNN_MR_CASE(16, 1, 8) WRNN_MR_CASE(16, 2, 8) WRNN_MR_CASE(16, 4, 8)
-    WRNN_MR_CASE(16, 16, 8)
-    WRNN_MR_CASE(4, 2, 2) WRNN_MR_CASE(4, 1, 1) WRNN_MR_CASE(4, 4, 4) WRNN_MR_CASE(4, 2, 1)
-    WRNN_MR_CASE(4, 1, 2) WRNN_MR_CASE(4, 4, 2) WRNN_MR_CASE(4, 2, 4) WRNN_MR_CASE(4, 4, 1)
-    WRNN_MR_CASE(4, 1, 4)
+    WRNN_MR_FORMS(WRNN_MR_CASE)
 #undef WRNN_MR_CASE
     return WRNN_EUNSUPPORTED;
 }
