@@ -249,6 +249,80 @@ int wrnn_postprocess(const float *y, int rows, int steps, int batched, int overl
 int wrnn_philox_draws(uint64_t seed, int64_t row_offset, int rows, int step0, int steps, int K, int mode, float *out,
                       void *stream);
 
+/* ---- streaming synthesis (round-7 addition, same ABI) -------------------------------------
+ * Push mel frames as the acoustic model produces them, pull float64 audio as soon as it is final.
+ * What generate(mels, None, False, …) computes, unbatched MoL, in pieces: the recurrent state stays
+ * on the GPU between calls, the persistent kernel is relaunched per push from that state, and the
+ * conditioning terms are formed at frame rate over a window of the running mel.
+ *
+ * Emission rule.  A sample of frame f reads mel frames up to f + pad (its aux frame, a MelResNet
+ * window of ±pad frames; the upsampling cascade reaches no further, wrnn_frame_weights), and a
+ * launch that ends before the utterance does also reads the conditioning of the one step after
+ * its last, which falls into the next frame.  Hence
+ *     lookahead = pad + 1 frames                                  (wrnn_stream_lookahead)
+ * and with R frames received and the end not yet seen
+ *     steps_done = max(0, R − lookahead) · hop
+ *     audio_done = min(steps_done, (T − 1) · hop)                 when total_frames = T was given
+ *                = min(steps_done, max(0, (R − 21) · hop))        when the total is unknown: the
+ *                  fade-out covers the last 20·hop of the (T − 1)·hop samples, and T >= R
+ * both functions of R alone, not of how the frames were chunked.  `final` (R = T) runs the loop to
+ * T·hop steps, as generate() does, and releases the rest: audio_done = (T − 1)·hop, the positions
+ * inside the last 20·hop multiplied by the same linspace(1, 0, 20·hop) element as wrnn_postprocess.
+ * WRNN_EINVAL: final with T < 21 (as wrnn_postprocess), or T != total_frames when that was given. */
+typedef struct wrnn_stream wrnn_stream_t;
+
+/* Open a session of U = 1..8 utterances advancing in lock step (one per XCD) on handle `h`.
+ *   ucfg, mcfg        the UpsampleNetwork's cascade and MelResNet (copied; taps are host pointers)
+ *   melresnet_packed  wrnn_melresnet's packed weights (device; the caller keeps them alive and
+ *                     unchanged until wrnn_stream_close)
+ *   total_frames      T when known up front, else −1
+ *   noise             [noise_steps][U][11] injected draws by absolute step (device; kept by the
+ *                     caller until close), or NULL for in-kernel Philox keyed (seed, row_offset + u,
+ *                     absolute step) — the draws a one-shot wrnn_generate_frames takes
+ * The session owns its recurrent state, hand-off tags, frame-term stores and mel tail: one-shot
+ * calls and other sessions on the same handle may run between its pushes, IN STREAM ORDER ON ONE
+ * STREAM — the handle's control words, membership counters and rocBLAS stream are shared and
+ * every persistent launch fills all XCDs, so work of one handle on two streams at once races (and
+ * two persistent grids would wait for each other).  Close every session before wrnn_destroy(h).
+ * Synchronous.
+ * WRNN_EUNSUPPORTED (message in wrnn_last_error(h)) unless U rows of this handle run on the dense
+ * one-row XCD kernel (last_path 5) or the block-sparse rnn-896 one (6), wrnn_frame_weights accepts
+ * the cascade and wrnn_melresnet the channel counts. */
+int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                     const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                     uint64_t seed, int64_t row_offset, wrnn_stream_t **out);
+
+/* Append n >= 0 mel frames and write the audio that became final.
+ *   mel   [U][feat_dims][n] (device; may be NULL when n = 0)
+ *   final nonzero: these are the last frames (n = 0, final = 1 flushes)
+ *   wave  [U][cap] float64 (device): utterance u's new samples at wave[u·cap .. u·cap + *n_out)
+ *   n_out samples per utterance written by this push = the growth of audio_done above: known on
+ *         return, without synchronising (wrnn_stream_plan gives it in advance; cap >= it)
+ * Queues its work on `stream` (one stream per handle, see wrnn_stream_open) and does not wait for
+ * it, EXCEPT when a session workspace has to grow: the workspaces are sized by the largest push
+ * so far (frame records, terms of n·hop + 1 steps, the held-back sample window, the frame-term
+ * stores) and growing one frees and reallocates it, which waits for the device.  A session fed
+ * pushes of at most the size of its first ones settles after a few pushes (the stores double);
+ * a larger push later synchronises once more.
+ * Kernel aborts surface through wrnn_check(h, stream); sets wrnn_info.last_path (5 or 6) and
+ * leaves wrnn_elapsed_ms at the last wrnn_generate's launch.  Argument errors (WRNN_EINVAL:
+ * counts against the rule above, cap, injected draws too short) are found before anything is
+ * queued and leave the session unchanged; any failure after that point kills the session
+ * (every later push returns WRNN_EINVAL: close it). */
+int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, double *wave, int cap, int *n_out,
+                     void *stream);
+
+/* The emission rule as a function (host only, stateless): the counts a session reports after
+ * frames_received frames (`final`: they were the last), total_frames as given to open (−1: unknown).
+ * Only ucfg's scales and pad are read.  WRNN_EINVAL as wrnn_stream_push. */
+int wrnn_stream_plan(const wrnn_upsample_cfg *ucfg, int frames_received, int final, int total_frames,
+                     int64_t *steps_done, int64_t *audio_done);
+
+/* lookahead of the rule above for this cascade: pad + 1 (negative WRNN_E* on a bad ucfg). */
+int wrnn_stream_lookahead(const wrnn_upsample_cfg *ucfg);
+
+void wrnn_stream_close(wrnn_stream_t *s);
+
 /* Message of the last failed stateless call on this thread. */
 const char *wrnn_cond_last_error(void);
 

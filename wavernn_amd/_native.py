@@ -20,7 +20,8 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_query", "wrnn_last_error", "wrnn_destroy", "wrnn_cond_shape", "wrnn_upsample_pack",
            "wrnn_postprocess", "wrnn_cond_last_error", "wrnn_generate_frames", "wrnn_generate_frames_rows",
            "wrnn_frame_weights", "wrnn_melresnet_floats", "wrnn_melresnet", "wrnn_philox_draws",
-           "wrnn_melresnet_tile_frames")
+           "wrnn_melresnet_tile_frames", "wrnn_stream_open", "wrnn_stream_push", "wrnn_stream_plan",
+           "wrnn_stream_lookahead", "wrnn_stream_close")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -108,6 +109,17 @@ def lib() -> ctypes.CDLL:
     L.wrnn_melresnet_tile_frames.restype = i32
     L.wrnn_philox_draws.argtypes = [u64, i64, i32, i32, i32, i32, i32, vp, vp]
     L.wrnn_philox_draws.restype = i32
+    L.wrnn_stream_open.argtypes = [vp, ctypes.POINTER(UpsampleCfg), ctypes.POINTER(MelResNetCfg), vp, i32, i32, vp, i32,
+                                   u64, i64, ctypes.POINTER(vp)]
+    L.wrnn_stream_open.restype = i32
+    L.wrnn_stream_push.argtypes = [vp, vp, i32, i32, vp, i32, pi, vp]
+    L.wrnn_stream_push.restype = i32
+    L.wrnn_stream_plan.argtypes = [ctypes.POINTER(UpsampleCfg), i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.wrnn_stream_plan.restype = i32
+    L.wrnn_stream_lookahead.argtypes = [ctypes.POINTER(UpsampleCfg)]
+    L.wrnn_stream_lookahead.restype = i32
+    L.wrnn_stream_close.argtypes = [vp]
+    L.wrnn_stream_close.restype = None
     L.wrnn_cond_last_error.argtypes = []
     L.wrnn_cond_last_error.restype = ctypes.c_char_p
     _lib = L

@@ -7,6 +7,8 @@
 #include <rocblas/rocblas.h>
 
 #include <algorithm>
+#include <climits>
+#include <memory>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -64,6 +66,13 @@ hipError_t launch_philox_fill(float *out, unsigned long long seed, long long row
 hipError_t launch_dx(const DxArgs &a, hipStream_t st);
 hipError_t prepare_dx_kernel(int max_lds_bytes, bool *ok);
 int cond_fail(int code, const std::string &m);
+// streaming sessions: the windowed terms pass and mel window (frame_terms.hip), the float64 post (condition.hip)
+hipError_t launch_terms_interp_win(const float *FT, int ft_base, const float *AT, int at_base, const float *coef,
+                                   float *T, int N, int U, int hop, int nJ, int t0, int nt, hipStream_t st);
+hipError_t launch_stream_mel_window(const float *tail_old, const float *chunk, int U, int feat, int n, int R_old,
+                                    int keep, int w0, int wn, float *win, float *tail_new, hipStream_t st);
+hipError_t launch_postprocess_stream(const float *y, int U, int y_ld, int y_t0, int p0, int m, int wave_len,
+                                     int fade_len, double *wave, int cap, hipStream_t st);
 }  // namespace wrnn
 
 using namespace wrnn;
@@ -2533,6 +2542,392 @@ int wrnn_generate_frames_rows(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const fl
     fs.stride = target > 0 ? target + overlap : 0;
     fs.coef = h->d_coef;
     return run_loop(h, path, nullptr, &fs, B, L, noise, seed, row_offset, out, labels, st);
+}
+
+// ---- streaming sessions (wavernn_amd.h: wrnn_stream_*) ------------------------------------
+// Rows [base, end) of `row` floats each in absolute numbering, appended at `end`; rows behind
+// keep_from may go.  When the live buffer is full the kept rows move to the front of the other one
+// (so the copy never overlaps), which is then the live one: old rows are copied, never recomputed.
+struct RowWin {
+    float *buf[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};   // floats
+    int cur = 0;
+    long long base = 0, end = 0;
+    size_t row = 0;
+    float *at(long long r) { return buf[cur] + (size_t)(r - base) * row; }
+};
+
+static int win_reserve(wrnn_t *h, RowWin &w, long long keep_from, long long add, hipStream_t st) {
+    keep_from = std::min(std::max(keep_from, w.base), w.end);
+    if ((size_t)(w.end + add - w.base) * w.row <= w.cap[w.cur]) return WRNN_OK;
+    const int o = 1 - w.cur;
+    const size_t need = (size_t)(w.end - keep_from + add) * w.row;
+    // ensure() frees through hipFree, which waits for the device: no launch in flight reads buf[o]
+    if (need > w.cap[o]) HIP_TRY(h, ensure(w.buf[o], w.cap[o], 2 * need));
+    if (w.end > keep_from)
+        HIP_TRY(h, hipMemcpyAsync(w.buf[o], w.at(keep_from), (size_t)(w.end - keep_from) * w.row * sizeof(float),
+                                  hipMemcpyDeviceToDevice, st));
+    w.cur = o;
+    w.base = keep_from;
+    return WRNN_OK;
+}
+
+struct wrnn_stream {
+    wrnn_t *h = nullptr;
+    int device = 0;
+    LoopPath path = P_XCD;
+    int U = 0, T_known = -1;
+    wrnn_upsample_cfg ucfg{};
+    std::vector<float> taps[4];
+    wrnn_melresnet_cfg mcfg{};
+    const float *mr_packed = nullptr, *noise = nullptr;
+    int noise_steps = 0;
+    uint64_t seed = 0;
+    int64_t row_offset = 0;
+    int hop = 1, nJ = 1, jlo = 0, pad = 0;
+    int N = 0, state_w = 0;
+    // progress: frames received, aux frames formed, loop steps run, samples emitted
+    int R = 0, A = 0, steps = 0, audio = 0;
+    bool fin = false, dead = false, primed = false;
+    // device state of the session
+    float *d_coef = nullptr, *d_state = nullptr, *d_tail[2] = {nullptr, nullptr};
+    unsigned long long *d_xg = nullptr;
+    int tail_cur = 0;
+    RowWin FT, AT;                  // W·(mel frame) rows i = frame − jlo, W·(aux frame, ones) rows f
+    float *d_y[2] = {nullptr, nullptr};   // fp32 loop samples not yet emitted: [U][y_ld], column 0 = step y_t0
+    size_t y_cap[2] = {0, 0};
+    int y_ld[2] = {0, 0}, y_cur = 0, y_t0 = 0;
+    // per-push workspaces
+    float *d_win = nullptr, *d_aux = nullptr, *d_frec = nullptr, *d_X = nullptr, *d_T = nullptr;
+    size_t win_cap = 0, aux_cap = 0, frec_cap = 0, X_cap = 0, T_cap = 0;
+};
+
+static int hop_of(const wrnn_upsample_cfg *c, int *hop) {
+    if (!c || c->n_scales < 1 || c->n_scales > 4 || c->pad < 0) return WRNN_EINVAL;
+    long long hh = 1;
+    for (int i = 0; i < c->n_scales; ++i) {
+        if (c->scales[i] < 1) return WRNN_EINVAL;
+        hh *= c->scales[i];
+    }
+    if (hh > (1 << 20)) return WRNN_EINVAL;
+    *hop = (int)hh;
+    return WRNN_OK;
+}
+
+// The emission rule of wavernn_amd.h: counts after R frames.  msg: why it is WRNN_EINVAL.
+static int stream_counts(int hop, int look, long long R, bool final, long long T_known, long long *steps,
+                         long long *audio, std::string *msg) {
+    const long long kFadeFrames = 20;   // generate()'s fade-out: 20·hop_length samples (fatchord_version.py:255-258)
+    if (R < 0 || T_known < -1) {
+        *msg = "negative frame count";
+        return WRNN_EINVAL;
+    }
+    const long long T = final ? R : T_known;
+    if (final && T_known >= 0 && R != T_known) {
+        *msg = "final after " + std::to_string(R) + " frames, total_frames was " + std::to_string(T_known);
+        return WRNN_EINVAL;
+    }
+    if (!final && T_known >= 0 && R > T_known) {
+        *msg = std::to_string(R) + " frames pushed, total_frames was " + std::to_string(T_known);
+        return WRNN_EINVAL;
+    }
+    if (T >= 0 && T < kFadeFrames + 1) {
+        *msg = "operands could not be broadcast together: the fade-out (20*hop_length = " +
+               std::to_string(kFadeFrames * hop) + ") is longer than the waveform (" +
+               std::to_string(std::max(0LL, T - 1) * hop) + ")";
+        return WRNN_EINVAL;
+    }
+    if ((std::max(R, T) + 1) * hop > (1LL << 31) - 1) {
+        *msg = "step index past 2^31";
+        return WRNN_EINVAL;
+    }
+    if (final) {
+        *steps = T * hop;
+        *audio = (T - 1) * hop;
+    } else {
+        *steps = std::max(0LL, R - look) * hop;
+        *audio = std::min(*steps, T >= 0 ? (T - 1) * hop : std::max(0LL, (R - (kFadeFrames + 1)) * hop));
+    }
+    return WRNN_OK;
+}
+
+int wrnn_stream_lookahead(const wrnn_upsample_cfg *ucfg) {
+    int hop = 1;
+    if (int rc = hop_of(ucfg, &hop)) return cond_fail(rc, "bad upsample config");
+    return ucfg->pad + 1;
+}
+
+int wrnn_stream_plan(const wrnn_upsample_cfg *ucfg, int frames_received, int final, int total_frames,
+                     int64_t *steps_done, int64_t *audio_done) {
+    int hop = 1;
+    if (int rc = hop_of(ucfg, &hop)) return cond_fail(rc, "bad upsample config");
+    long long s = 0, a = 0;
+    std::string msg;
+    if (int rc = stream_counts(hop, ucfg->pad + 1, frames_received, final != 0, total_frames, &s, &a, &msg))
+        return cond_fail(rc, msg);
+    if (steps_done) *steps_done = s;
+    if (audio_done) *audio_done = a;
+    return WRNN_OK;
+}
+
+void wrnn_stream_close(wrnn_stream_t *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    for (void *p : {(void *)s->d_coef, (void *)s->d_state, (void *)s->d_tail[0],
+                    (void *)s->d_tail[1], (void *)s->d_xg, (void *)s->FT.buf[0], (void *)s->FT.buf[1],
+                    (void *)s->AT.buf[0], (void *)s->AT.buf[1], (void *)s->d_y[0], (void *)s->d_y[1], (void *)s->d_win,
+                    (void *)s->d_aux, (void *)s->d_frec, (void *)s->d_X, (void *)s->d_T})
+        if (p) (void)hipFree(p);   // hipFree waits for the device: no push in flight uses them
+    delete s;
+}
+
+int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                     const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                     uint64_t seed, int64_t row_offset, wrnn_stream_t **out) {
+    if (!h) return WRNN_EINVAL;
+    if (!out) return fail(h, WRNN_EINVAL, "need out");
+    *out = nullptr;
+    if (!h->ready) return fail(h, WRNN_ENOWEIGHTS, "weights not (fully) set");
+    if (!ucfg || !mcfg || !melresnet_packed) return fail(h, WRNN_EINVAL, "need ucfg, mcfg and the packed MelResNet");
+    if (U < 1 || U > kXcds) return fail(h, WRNN_EINVAL, "a session has 1.." + std::to_string(kXcds) + " utterances");
+    if (total_frames < -1) return fail(h, WRNN_EINVAL, "total_frames is a frame count or -1");
+    if (noise && noise_steps < 1) return fail(h, WRNN_EINVAL, "noise needs noise_steps >= 1");
+    if (h->dm || h->cfg.mode != WRNN_MODE_MOL)
+        return fail(h, WRNN_EUNSUPPORTED, "streaming sessions run the one-row XCD MoL kernels: this handle is not MoL");
+    const LoopPath path = choose_path(h, U);
+    if (path != P_XCD && path != P_XCDS)
+        return fail(h, WRNN_EUNSUPPORTED,
+                    "streaming sessions run the dense rnn/fc 512 XCD kernel or the block-sparse rnn 896 one; " +
+                        std::to_string(U) + " row(s) of this handle take loop path " + std::to_string((int)path));
+    const int feat = h->cfg.feat_dims, A4 = h->CD - feat;
+    if (ucfg->feat_dims != feat || ucfg->res_out_dims != A4 || mcfg->in_dims != feat || mcfg->res_out_dims != A4 ||
+        mcfg->pad != ucfg->pad)
+        return fail(h, WRNN_EINVAL, "upsample / MelResNet config does not match the handle's feat / aux dims");
+    if (ucfg->n_scales < 1 || ucfg->n_scales > 4) return fail(h, WRNN_EINVAL, "1..4 upsample scales");
+    for (int i = 0; i < ucfg->n_scales; ++i)
+        if (ucfg->scales[i] < 1 || !ucfg->taps[i]) return fail(h, WRNN_EINVAL, "bad upsample scale / taps");
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::unique_ptr<wrnn_stream, void (*)(wrnn_stream *)> s(new wrnn_stream, wrnn_stream_close);
+    s->h = h;
+    s->device = h->device;
+    s->path = path;
+    s->U = U;
+    s->T_known = total_frames;
+    s->ucfg = *ucfg;
+    for (int i = 0; i < ucfg->n_scales; ++i) {
+        s->taps[i].assign(ucfg->taps[i], ucfg->taps[i] + 2 * ucfg->scales[i] + 1);
+        s->ucfg.taps[i] = s->taps[i].data();
+    }
+    s->mcfg = *mcfg;
+    s->mr_packed = melresnet_packed;
+    s->noise = noise;
+    s->noise_steps = noise_steps;
+    s->seed = seed;
+    s->row_offset = row_offset;
+    s->pad = ucfg->pad;
+    std::vector<float> coef;
+    if (!frame_weights(s->ucfg, &s->hop, &s->nJ, &s->jlo, coef))
+        return fail(h, WRNN_EUNSUPPORTED,
+                    "the upsample cascade has no exact frame-rate form (pad frames < its reach, or more than 8 taps)");
+    if (total_frames >= 0) {   // the same refusal final would give, before any work
+        long long st_ = 0, au_ = 0;
+        std::string msg;
+        if (int rc = stream_counts(s->hop, s->pad + 1, 0, false, total_frames, &st_, &au_, &msg)) return fail(h, rc, msg);
+    }
+    const int tile = wrnn_melresnet_tile_frames(mcfg, U, 1);
+    if (tile < 0) return fail(h, tile, "the MelResNet kernel does not cover these channel counts");
+    s->N = kXcdWgs * (path == P_XCD ? kXTerms : kSTerms);
+    s->state_w = path == P_XCD ? kXStateW : kSStateW;
+    s->FT.row = s->AT.row = (size_t)U * s->N;
+    const size_t tail_n = (size_t)std::max(1, 2 * s->pad) * U * feat;
+    HIP_TRY(h, hipMalloc(&s->d_coef, coef.size() * sizeof(float)));
+    HIP_TRY(h, hipMalloc(&s->d_state, (size_t)U * kXcdWgs * s->state_w * sizeof(float)));
+    HIP_TRY(h, hipMalloc(&s->d_xg, (size_t)U * kXXcdStride * 8));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(h, hipMalloc(&s->d_tail[i], tail_n * sizeof(float)));
+        HIP_TRY(h, hipMemset(s->d_tail[i], 0, tail_n * sizeof(float)));
+    }
+    HIP_TRY(h, hipMemcpy(s->d_coef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(s->d_xg, 0, (size_t)U * kXXcdStride * 8));   // hop tags are step + 1: they start at 1
+    HIP_TRY(h, hipMemset(s->d_state, 0, (size_t)U * kXcdWgs * s->state_w * sizeof(float)));
+    if (!h->d_members) HIP_TRY(h, hipMalloc(&h->d_members, kXcds * sizeof(int)));
+    HIP_TRY(h, hipDeviceSynchronize());   // the memsets are asynchronous to the host
+    *out = s.release();
+    return WRNN_OK;
+}
+
+// One persistent launch per time chunk of the steps [t_begin, t_end) of a push, through the kernel's
+// own launcher; `last`: the utterance ends at t_end.
+extern "C++" {
+template <typename Args, typename Slab>
+static int stream_launches(wrnn_stream *s, int t_begin, int t_end, bool last, const Slab &slab,
+                           hipError_t (*launch)(const Args &, hipStream_t), hipStream_t st) {
+    wrnn_t *h = s->h;
+    const char *mb_env = std::getenv("WRNN_TERMS_MB");
+    const double budget = (mb_env ? std::atof(mb_env) : 8192.0) * (1 << 20) / 4.0;   // floats
+    const int Lc_max = (int)std::max(1.0, std::min((double)(t_end - t_begin), budget / ((double)s->U * s->N) - 1.0));
+    HIP_TRY(h, ensure(s->d_T, s->T_cap, (size_t)(Lc_max + 1) * s->U * s->N));
+    for (int t0 = t_begin; t0 < t_end; t0 += Lc_max) {
+        const int Lc = std::min(Lc_max, t_end - t0);
+        // one step ahead (the kernels prefetch the terms of t + 1), unless the utterance ends there
+        const int rows = last ? std::min(Lc + 1, t_end - t0) : Lc + 1;
+        HIP_TRY(h, launch_terms_interp_win(s->FT.buf[s->FT.cur], (int)s->FT.base, s->AT.buf[s->AT.cur], (int)s->AT.base,
+                                           s->d_coef, s->d_T, s->N, s->U, s->hop, s->nJ, t0, rows, st));
+        HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
+        Args a{};
+        a.slab = h->d_xslab;
+        a.terms = s->d_T;
+        a.noise = s->noise;
+        a.out = s->d_y[s->y_cur];
+        a.state = s->d_state;
+        a.xg = s->d_xg;
+        a.members = h->d_members;
+        a.ctl = h->d_ctl;
+        a.seed = s->seed;
+        a.row0 = s->row_offset;
+        a.timeout_ticks = h->timeout_ticks;
+        // the end is in sight only in the last push; until then the loop horizon lies past every chunk
+        a.L = last ? t_end : INT_MAX;
+        a.windowed = 1;
+        a.nz_hor = s->noise ? s->noise_steps : INT_MAX;
+        a.out_ld = s->y_ld[s->y_cur];
+        a.out_t0 = s->y_t0;
+        a.t0 = t0;
+        a.Lc = Lc;
+        a.Bt = s->U;
+        a.b0 = 0;
+        a.nb = s->U;
+        a.s = slab;
+        a.dbg = nullptr;
+        a.dbg_steps = 0;
+        HIP_TRY(h, launch(a, st));
+    }
+    return WRNN_OK;
+}
+}  // extern "C++"
+
+static int stream_push(wrnn_stream *s, const float *mel, int n, bool final, double *wave, int cap, int *n_out,
+                       hipStream_t st) {
+    wrnn_t *h = s->h;
+    const int U = s->U, feat = h->cfg.feat_dims, A4 = h->CD - feat, KX = h->KXc, N = s->N, pad = s->pad;
+    const int jhi = s->jlo + s->nJ - 1;
+    long long S_new = 0, Au_new = 0;
+    std::string msg;
+    if (int rc = stream_counts(s->hop, pad + 1, (long long)s->R + n, final, s->T_known, &S_new, &Au_new, &msg))
+        return fail(h, rc, msg);
+    const int m = (int)(Au_new - s->audio);
+    if (m > 0 && (!wave || cap < m))
+        return fail(h, WRNN_EINVAL, "this push emits " + std::to_string(m) + " samples per utterance: wave holds " +
+                                        std::to_string(wave ? cap : 0));
+    if (s->noise && S_new > s->noise_steps)
+        return fail(h, WRNN_EINVAL, "the injected draws cover " + std::to_string(s->noise_steps) + " steps, the loop reaches " +
+                                        std::to_string(S_new));
+    // From here on work is queued and the session's stores advance: a failure on the way, whatever
+    // its code, leaves them out of step with the frame counts, so the session is dead until the end
+    s->dead = true;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!h->blas && rocblas_create_handle(&h->blas) != rocblas_status_success)
+        return fail(h, WRNN_EHIP, "rocblas_create_handle failed");
+    if (rocblas_set_stream(h->blas, st) != rocblas_status_success) return fail(h, WRNN_EHIP, "rocblas_set_stream failed");
+    const float one = 1.0f, zero = 0.0f;
+    // C[m][N] = W·X for `frames` frame records in d_frec, through the path's terms GEMM
+    auto gemm = [&](int frames, float ones, float *C) -> int {
+        HIP_TRY(h, ensure(s->d_X, s->X_cap, (size_t)frames * U * KX));
+        HIP_TRY(h, launch_pack_cond_input(s->d_frec, h->CD, U, 0, U, 0, frames, KX, s->d_X, st, 0, ones));
+        if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, frames * U, KX, &one, h->d_xWt,
+                          KX, s->d_X, KX, &zero, C, N) != rocblas_status_success)
+            return fail(h, WRNN_EHIP, "rocblas_sgemm (frame terms) failed");
+        return WRNN_OK;
+    };
+    const int R_old = s->R, R_new = R_old + n;
+    const long long keep_f = s->steps / s->hop;   // the frame of the next loop step: rows behind it are done with
+    HIP_TRY(h, ensure(s->d_frec, s->frec_cap, (size_t)(std::max(n, 1) + pad) * U * h->CD));
+    if (!s->primed) {   // the zero FT rows of the mel frames before frame 0
+        if (s->jlo < 0) {
+            if (int rc = win_reserve(h, s->FT, 0, -s->jlo, st)) return rc;
+            HIP_TRY(h, hipMemsetAsync(s->FT.at(0), 0, (size_t)(-s->jlo) * s->FT.row * sizeof(float), st));
+            s->FT.end = -s->jlo;
+        }
+        s->primed = true;
+    }
+    // aux frames that became computable: frame f needs the mel up to f + pad (zeros once the end is known)
+    const int A_new = final ? R_new : std::max(s->A, R_new - pad);
+    const int Tw = A_new - s->A, wn = Tw > 0 ? Tw + 2 * pad : 0;
+    if (n > 0 || Tw > 0) {
+        HIP_TRY(h, ensure(s->d_win, s->win_cap, (size_t)std::max(1, wn) * U * feat));
+        HIP_TRY(h, launch_stream_mel_window(s->d_tail[s->tail_cur], mel, U, feat, n, R_old, 2 * pad, s->A - pad, wn,
+                                            s->d_win, s->d_tail[1 - s->tail_cur], st));
+        s->tail_cur = 1 - s->tail_cur;
+    }
+    // FT rows of the new mel frames (row i = frame − jlo), and zero rows past the last frame
+    const int ft_zero = final ? std::max(0, jhi) : 0;
+    if (n > 0 || ft_zero > 0) {
+        if (int rc = win_reserve(h, s->FT, keep_f, n + ft_zero, st)) return rc;
+        if (n > 0) {
+            HIP_TRY(h, launch_frame_cond(mel, nullptr, U, feat, A4, n, n, 0, 0, s->d_frec, st));
+            if (int rc = gemm(n, 0.0f, s->FT.at(s->FT.end))) return rc;
+            s->FT.end += n;
+        }
+        if (ft_zero > 0) {
+            HIP_TRY(h, hipMemsetAsync(s->FT.at(s->FT.end), 0, (size_t)ft_zero * s->FT.row * sizeof(float), st));
+            s->FT.end += ft_zero;
+        }
+    }
+    if (Tw > 0) {
+        HIP_TRY(h, ensure(s->d_aux, s->aux_cap, (size_t)U * A4 * Tw));
+        if (int rc = wrnn_melresnet(&s->mcfg, s->mr_packed, s->d_win, U, Tw, s->d_aux, st))
+            return fail(h, rc, std::string("wrnn_melresnet: ") + wrnn_cond_last_error());
+        if (int rc = win_reserve(h, s->AT, keep_f, Tw, st)) return rc;
+        HIP_TRY(h, ensure(s->d_frec, s->frec_cap, (size_t)Tw * U * h->CD));
+        HIP_TRY(h, launch_frame_cond(nullptr, s->d_aux, U, feat, A4, Tw, Tw, 0, 1, s->d_frec, st));
+        if (int rc = gemm(Tw, 1.0f, s->AT.at(s->AT.end))) return rc;
+        s->AT.end += Tw;
+    }
+    // the loop over the steps that became runnable, into the not-yet-emitted sample window
+    const int S_old = s->steps;
+    if (S_new > S_old) {
+        const int held = S_old - s->audio;   // samples run but still held back
+        if ((int)S_new - s->y_t0 > s->y_ld[s->y_cur]) {
+            const int o = 1 - s->y_cur, need = (int)S_new - s->audio;
+            if ((size_t)need * U > s->y_cap[o]) HIP_TRY(h, ensure(s->d_y[o], s->y_cap[o], (size_t)2 * need * U));
+            s->y_ld[o] = (int)(s->y_cap[o] / U);
+            if (held > 0)
+                HIP_TRY(h, hipMemcpy2DAsync(s->d_y[o], (size_t)s->y_ld[o] * 4, s->d_y[s->y_cur] + (s->audio - s->y_t0),
+                                            (size_t)s->y_ld[s->y_cur] * 4, (size_t)held * 4, U, hipMemcpyDeviceToDevice, st));
+            s->y_cur = o;
+            s->y_t0 = s->audio;
+        }
+        HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
+        h->last_path = (int)s->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
+        int rc;
+        if (s->path == P_XCD) rc = stream_launches<XcdArgs>(s, S_old, (int)S_new, final, h->xs, launch_xcd, st);
+        else rc = stream_launches<XcdsArgs>(s, S_old, (int)S_new, final, h->xss, launch_xcds, st);
+        if (rc) return rc;
+    }
+    if (m > 0) {
+        const int T = final ? R_new : s->T_known;
+        HIP_TRY(h, launch_postprocess_stream(s->d_y[s->y_cur], U, s->y_ld[s->y_cur], s->y_t0, s->audio, m,
+                                             T >= 0 ? (T - 1) * s->hop : -1, 20 * s->hop, wave, cap, st));
+    }
+    s->R = R_new;
+    s->A = A_new;
+    s->steps = (int)S_new;
+    s->audio = (int)Au_new;
+    s->fin = final;
+    s->dead = false;
+    if (n_out) *n_out = m;
+    return WRNN_OK;
+}
+
+int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, double *wave, int cap, int *n_out,
+                     void *stream) {
+    if (!s || !s->h) return WRNN_EINVAL;
+    wrnn_t *h = s->h;
+    if (n_out) *n_out = 0;
+    if (s->dead) return fail(h, WRNN_EINVAL, "the session failed in an earlier push: close it");
+    if (s->fin) return fail(h, WRNN_EINVAL, "push after the final one: the session is finished");
+    if (n < 0 || (n > 0 && !mel) || cap < 0) return fail(h, WRNN_EINVAL, "need n >= 0, mel when n > 0, cap >= 0");
+    return stream_push(s, mel, n, final != 0, wave, cap, n_out, (hipStream_t)stream);
 }
 
 int wrnn_check(wrnn_t *h, void *stream) {

@@ -216,6 +216,40 @@ __global__ void postprocess_kernel(PostArgs a) {
     a.wave[t] = v;
 }
 
+// postprocess_kernel's unbatched MoL case for a streaming session (wrnn_stream_push): the loop
+// samples at absolute positions [p0, p0 + m) of U utterances → float64, position p of utterance u
+// at wave[u·cap + p − p0].  wave_len < 0: the total is not known yet (the caller emits no position
+// the fade could reach); else the positions inside the last fade_len samples take the same
+// linspace(1, 0, fade_len) element as the one-shot kernel, by absolute position.
+struct PostStreamArgs {
+    const float *y;       // [U][y_ld], position p at column p − y_t0
+    double *wave;         // [U][cap]
+    int U, y_ld, y_t0, p0, m, cap, wave_len, fade_len;
+    double fout_step;
+};
+
+__global__ void postprocess_stream_kernel(PostStreamArgs a) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, u = blockIdx.y;
+    if (i >= a.m) return;
+    const int p = a.p0 + i;
+    double v = (double)a.y[(size_t)u * a.y_ld + (p - a.y_t0)];
+    if (a.wave_len >= 0) {
+        const int q = p - (a.wave_len - a.fade_len);
+        if (q >= 0) v = v * linspace_at(q, a.fade_len, 1.0, 0.0, a.fout_step);
+    }
+    a.wave[(size_t)u * a.cap + i] = v;
+}
+
+hipError_t launch_postprocess_stream(const float *y, int U, int y_ld, int y_t0, int p0, int m, int wave_len,
+                                     int fade_len, double *wave, int cap, hipStream_t st) {
+    if (m <= 0) return hipSuccess;
+    PostStreamArgs a{y, wave, U, y_ld, y_t0, p0, m, cap, wave_len, fade_len,
+                     (0.0 - 1.0) / (double)(fade_len > 1 ? fade_len - 1 : 1)};
+    hipLaunchKernelGGL(postprocess_stream_kernel, dim3((m + 255) / 256, U), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
 // error of the last failed stateless call on this thread (also capi.cpp's wrnn_philox_draws)
 thread_local std::string g_cond_err;
 int cond_fail(int code, const std::string &m) {

@@ -87,7 +87,7 @@ namespace wrnn {
                 (unsigned)__builtin_amdgcn_s_memrealtime();                                                   \
     } while (0)
 
-template <bool kDbg>
+template <bool kDbg, bool kWin>
 __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int R = 512, TW = kXcdWgs * kXTerms;
@@ -117,6 +117,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     const int b = a.b0 + k;
     const int t_end = a.t0 + a.Lc;
     const int t_terms = min(t_end, a.L - 1);
+    const int nz_hor = kWin ? a.nz_hor : a.L;   // the step below which injected draws exist
     unsigned long long *xg = a.xg + (size_t)k * kXXcdStride;
     auto XG = [&](int hop) { return xg + (size_t)hop * kXHopStride; };
     // publishes through one wave-uniform buffer descriptor + a 32-bit granule index (the 64-bit
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
         for (int t = a.t0; t < a.t0 + 3; ++t) {
             if (t <= t_terms)
                 for (int i = tid; i < kXTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];
-            if (wave == 1 && lane < 11 && t < a.L) NZ(t)[lane] = noise_term(t);
+            if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);
         }
     }
     const bool resume = a.t0 > 0;
@@ -460,7 +461,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
             x = mol_sample_pairs(la, lb, ua, ub, u10, jp);
             if (lane == 0) {
                 xs[t & 1] = x;
-                if (c == 0) a.out[(size_t)b * a.L + t] = x;
+                if (c == 0) a.out[kWin ? (size_t)b * a.out_ld + (t - a.out_t0) : (size_t)b * a.L + t] = x;
             }
             XSTAMP(8);
         } else if (wave < kXWaveFc2) {
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
                     if (t + 2 >= a.t0 + 3) {
                         if (t + 2 <= t_terms && lane < kXTerms / 4)
                             reinterpret_cast<f4v *>(RING(t + 2))[lane] = reinterpret_cast<const f4v *>(TERMS(t + 2))[lane];
-                        if (t + 2 < a.L && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
+                        if (t + 2 < nz_hor && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
                     }
                 }
                 goto step_end;
@@ -617,7 +618,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
                 // issued here and stored after the wave's W_hh2 pass: 3.25 -> 3.30 us/step)
                 if (t + 2 <= t_terms && lane < kXTerms / 4)
                     reinterpret_cast<f4v *>(RING(t + 2))[lane] = reinterpret_cast<const f4v *>(TERMS(t + 2))[lane];
-                if (t + 2 < a.L && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
+                if (t + 2 < nz_hor && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
                 XSTAMPW(12, 7);
             }
             wait_flag(h2ready, tag);
@@ -649,18 +650,19 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     if (tid == 0) st[512 + 2048 + 48 + 16] = xs[(t_end - 1) & 1];
 }
 
-#define WRNN_K_XCD fatchord_xcd_kernel<false>
-#define WRNN_K_XCD_DBG fatchord_xcd_kernel<true>
+#define WRNN_K_XCD fatchord_xcd_kernel<false, false>
+#define WRNN_K_XCD_DBG fatchord_xcd_kernel<true, false>
+#define WRNN_K_XCD_WIN fatchord_xcd_kernel<false, true>   // streaming sessions (no stamps)
 
 hipError_t launch_xcd(const XcdArgs &a, hipStream_t st) {
     XcdArgs args = a;
     void *params[] = {&args};
-    const void *kf = a.dbg ? (const void *)WRNN_K_XCD_DBG : (const void *)WRNN_K_XCD;
+    const void *kf = a.windowed ? (const void *)WRNN_K_XCD_WIN : a.dbg ? (const void *)WRNN_K_XCD_DBG : (const void *)WRNN_K_XCD;
     return hipLaunchKernel(kf, dim3(kXcds * kXcdWgs), dim3(kXThreads), params, xcd_lds_layout().total * sizeof(float), st);
 }
 
 hipError_t prepare_xcd_kernel(int max_lds_bytes) {
-    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG}) {
+    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN}) {
         hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
         if (e != hipSuccess) return e;
     }
@@ -669,7 +671,7 @@ hipError_t prepare_xcd_kernel(int max_lds_bytes) {
 
 hipError_t xcd_occupancy(int *blocks_per_cu) {
     int best = 1 << 30;
-    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG}) {
+    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN}) {
         int n = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kf, kXThreads, xcd_lds_layout().total * sizeof(float));
         if (e != hipSuccess) return e;

@@ -48,8 +48,8 @@ constexpr int kSStateW = 896 + 3584 + 84 + 28 + 4;
 struct XcdsArgs {
     const float *slab;            // [kXcdWgs][slab.total]
     const float *terms;           // [Lc + 1][nb][kXcdWgs·kSTerms], row (t - t0)·nb + k
-    const float *noise;           // [L][Bt][11] or nullptr (Philox)
-    float *out;                   // [Bt][L]
+    const float *noise;           // [L][Bt][11] (windowed: [nz_hor][Bt][11]), row = step, or nullptr (Philox)
+    float *out;                   // [Bt][L]; windowed: [Bt][out_ld], step t at column t − out_t0
     float *state;                 // [nb][kXcdWgs][kSStateW]
     unsigned long long *xg;       // [nb][kXXcdStride] granules
     int *members;                 // [kXcds] arrival counters (zeroed before the launch)
@@ -57,10 +57,17 @@ struct XcdsArgs {
     unsigned long long seed;
     long long row0;               // global row id of XCD 0's row (Philox key: row0 + k)
     long long timeout_ticks;
+    // Steps [t0, t0 + Lc) of a loop that goes on while t + 1 < L: the total length, or (windowed
+    // launches) anything past t0 + Lc while the end is unknown — the terms then hold the row of step
+    // t0 + Lc too
     int L, t0, Lc, Bt, b0, nb;
     XcdsSlab s;
     unsigned *dbg;                // [nb·32][dbg_steps][kStamps] or nullptr
     int dbg_steps;
+    // windowed launches (streaming sessions: a chunk of an utterance whose length may not be known
+    // yet; the kernel's kWin instantiation, which alone reads these): injected draws exist for
+    // steps < nz_hor, the output has its own leading dimension and time origin
+    int windowed, nz_hor, out_ld, out_t0;
 };
 
 struct XcdsLds {

@@ -173,7 +173,7 @@ __device__ __forceinline__ float sp_block_row(const f4v (&wa)[4], const f4v (&wb
                 (unsigned)__builtin_amdgcn_s_memrealtime();                                                   \
     } while (0)
 
-template <bool kDbg>
+template <bool kDbg, bool kWin>
 __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int R = kSR, TW = kXcdWgs * kSTerms;
@@ -206,6 +206,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     const int b = a.b0 + k;
     const int t_end = a.t0 + a.Lc;
     const int t_terms = min(t_end, a.L - 1);
+    const int nz_hor = kWin ? a.nz_hor : a.L;   // the step below which injected draws exist
     unsigned long long *xg = a.xg + (size_t)k * kXXcdStride;
     auto XG = [&](int hop) { return xg + (size_t)hop * kXHopStride; };
     const __amdgpu_buffer_rsrc_t xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);   // publishes
@@ -361,14 +362,14 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
         for (int t = a.t0; t < a.t0 + 3; ++t) {
             if (t <= t_terms)
                 for (int i = tid; i < kSTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];
-            if (wave == 1 && lane < 11 && t < a.L) NZ(t)[lane] = noise_term(t);
+            if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);
         }
     }
     // wave 7 stages the ring entries of a step in wg (its GRU2 registers, unused by wave 7):
     // conditioning terms (lanes < 57, one float4 each) and the injected sampler noise (lanes < 11)
     auto stage_ring = [&](int t) {
         if (t <= t_terms && lane < kSTerms / 4) wg[0] = reinterpret_cast<const f4v *>(TERMS(t))[lane];
-        if (a.noise && t < a.L && lane < 11) wg[1].x = a.noise[((size_t)t * a.Bt + b) * 11 + lane];
+        if (a.noise && t < nz_hor && lane < 11) wg[1].x = a.noise[((size_t)t * a.Bt + b) * 11 + lane];
     };
     if (wave == 7) stage_ring(a.t0 + 3);
     const bool resume = a.t0 > 0;
@@ -588,7 +589,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
                 x = mol_sample_pairs(la, lb, ua, ub, u10, jp);
                 if (lane == 0) {
                     xs[t & 1] = x;
-                    if (c == 0) a.out[(size_t)b * a.L + t] = x;
+                    if (c == 0) a.out[kWin ? (size_t)b * a.out_ld + (t - a.out_t0) : (size_t)b * a.L + t] = x;
                 }
                 XSTAMP(8);
             }
@@ -629,7 +630,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
                 XSTAMPW(11, 5);
                 if (wave == 7) {
                     if (t + 3 <= t_terms && lane < kSTerms / 4) reinterpret_cast<f4v *>(RING(t + 3))[lane] = wg[0];
-                    if (t + 3 < a.L && lane < 11)
+                    if (t + 3 < nz_hor && lane < 11)
                         NZ(t + 3)[lane] = mol_noise_term(a.noise ? wg[1].x : philox_noise(a.seed, prow, (uint32_t)(t + 3), (uint32_t)lane, 1), lane);
                     stage_ring(t + 4);
                     if (!WRNN_XCDS_GRU2_STAMPS) XSTAMPW(12, 7);
@@ -660,18 +661,19 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     if (tid == 0) st[oX] = xs[(t_end - 1) & 1];
 }
 
-#define WRNN_K_XCDS fatchord_xcds_kernel<false>
-#define WRNN_K_XCDS_DBG fatchord_xcds_kernel<true>
+#define WRNN_K_XCDS fatchord_xcds_kernel<false, false>
+#define WRNN_K_XCDS_DBG fatchord_xcds_kernel<true, false>
+#define WRNN_K_XCDS_WIN fatchord_xcds_kernel<false, true>   // streaming sessions (no stamps)
 
 hipError_t launch_xcds(const XcdsArgs &a, hipStream_t st) {
     XcdsArgs args = a;
     void *params[] = {&args};
-    const void *kf = a.dbg ? (const void *)WRNN_K_XCDS_DBG : (const void *)WRNN_K_XCDS;
+    const void *kf = a.windowed ? (const void *)WRNN_K_XCDS_WIN : a.dbg ? (const void *)WRNN_K_XCDS_DBG : (const void *)WRNN_K_XCDS;
     return hipLaunchKernel(kf, dim3(kXcds * kXcdWgs), dim3(kXThreads), params, xcds_lds_layout().total * sizeof(float), st);
 }
 
 hipError_t prepare_xcds_kernel(int max_lds_bytes) {
-    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG}) {
+    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN}) {
         hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
         if (e != hipSuccess) return e;
     }
@@ -680,7 +682,7 @@ hipError_t prepare_xcds_kernel(int max_lds_bytes) {
 
 hipError_t xcds_occupancy(int *blocks_per_cu) {
     int best = 1 << 30;
-    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG}) {
+    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN}) {
         int n = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kf, kXThreads, xcds_lds_layout().total * sizeof(float));
         if (e != hipSuccess) return e;

@@ -122,4 +122,98 @@ hipError_t launch_terms_interp(const float *FT, const float *AT, const float *co
     return hipGetLastError();
 }
 
+// ---- streaming sessions (wrnn_stream_*): the same pass over a WINDOW of frame rows ---------------
+// A session appends FT / AT rows as mel frames arrive and drops the rows behind the loop, so the
+// stores hold rows [ft_base, …) / [at_base, …) of the absolute numbering above (FT row i = mel frame
+// i + jlo, AT row f = aux frame f).  Loop row k is utterance k (unbatched: nf = 1), and an unbatched
+// loop has no step past its utterance (the last launch forms no terms row beyond step T·hop − 1),
+// so neither the frame count nor a W·[0 | 0 | 1] row enters: every step reads its own frame's rows.
+// The per-sample fmaf order is terms_interp_kernel's.
+struct InterpWinArgs {
+    const float *FT;      // [rows][U][N], row 0 = absolute row ft_base
+    const float *AT;      // [rows][U][N], row 0 = absolute row at_base
+    const float *coef;    // [hop][nJ]
+    float *T;             // [nt · nb][N]  record (t − t0)·nb + k
+    int N, U, hop, nJ;
+    int ft_base, at_base;
+    int nb, t0, nt;
+};
+
+__global__ __launch_bounds__(kInterpThreads) void terms_interp_win_kernel(InterpWinArgs a) {
+    const int c4 = blockIdx.y * kInterpThreads + threadIdx.x;   // float4 column
+    if (4 * c4 >= a.N) return;
+    const int nblk = (a.nt + kInterpSteps - 1) / kInterpSteps;
+    const int k = blockIdx.x / nblk, tb = (blockIdx.x - k * nblk) * kInterpSteps;
+    const size_t rs = (size_t)a.U * a.N;                         // frame-row stride
+    const float *A0 = a.AT + (size_t)k * a.N + 4 * c4, *F0 = a.FT + (size_t)k * a.N + 4 * c4;
+    float4 fr[kInterpMaxJ], ar = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int loaded = -1;
+    for (int i = 0; i < kInterpSteps; ++i) {
+        const int tl = tb + i;
+        if (tl >= a.nt) break;
+        const int p = a.t0 + tl;
+        const int f = p / a.hop;
+        if (f != loaded) {
+            ar = *reinterpret_cast<const float4 *>(A0 + (size_t)(f - a.at_base) * rs);
+#pragma unroll
+            for (int j = 0; j < kInterpMaxJ; ++j)
+                if (j < a.nJ) fr[j] = *reinterpret_cast<const float4 *>(F0 + (size_t)(f + j - a.ft_base) * rs);
+            loaded = f;
+        }
+        float4 acc = ar;
+        const float *cf = a.coef + (size_t)(p - f * a.hop) * a.nJ;
+#pragma unroll
+        for (int j = 0; j < kInterpMaxJ; ++j) {
+            if (j < a.nJ) {
+                const float w = cf[j];
+                acc.x = fmaf(w, fr[j].x, acc.x);
+                acc.y = fmaf(w, fr[j].y, acc.y);
+                acc.z = fmaf(w, fr[j].z, acc.z);
+                acc.w = fmaf(w, fr[j].w, acc.w);
+            }
+        }
+        *reinterpret_cast<float4 *>(a.T + ((size_t)tl * a.nb + k) * a.N + 4 * c4) = acc;
+    }
+}
+
+// The caller holds FT rows [t0 / hop, (t0 + nt − 1) / hop + nJ) and AT rows [t0 / hop, (t0 + nt − 1) / hop]
+// in its stores; N % 4 == 0, nJ <= kInterpMaxJ, nb == U.
+hipError_t launch_terms_interp_win(const float *FT, int ft_base, const float *AT, int at_base, const float *coef,
+                                   float *T, int N, int U, int hop, int nJ, int t0, int nt, hipStream_t st) {
+    InterpWinArgs a{FT, AT, coef, T, N, U, hop, nJ, ft_base, at_base, U, t0, nt};
+    const dim3 grid(U * ((nt + kInterpSteps - 1) / kInterpSteps), (N / 4 + kInterpThreads - 1) / kInterpThreads);
+    hipLaunchKernelGGL(terms_interp_win_kernel, grid, dim3(kInterpThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+// The MelResNet input of a session's newly computable aux frames, and its carried mel tail, in one
+// pass.  Frame g of the running mel is 0 outside [0, R_old + n) (pad_tensor's zeros: before the
+// first frame and, once the end is known, after the last), chunk[:, g − R_old] for the frames of
+// this push and tail_old[g − (R_old − keep)] for the `keep` frames before it.
+//   chunk [U][feat][n], tail_old / tail_new [keep][U][feat], win [U][feat][wn] = frames w0 .. w0 + wn − 1,
+//   tail_new = frames R_old + n − keep .. R_old + n − 1
+__global__ void stream_mel_window_kernel(const float *__restrict__ tail_old, const float *__restrict__ chunk, int U,
+                                         int feat, int n, int R_old, int keep, int w0, int wn,
+                                         float *__restrict__ win, float *__restrict__ tail_new) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int W = wn + keep;
+    if (idx >= U * feat * W) return;
+    const int j = idx % W, uc = idx / W, c = uc % feat, u = uc / feat;
+    const int g = j < wn ? w0 + j : R_old + n - keep + (j - wn);
+    float v = 0.0f;
+    if (g >= R_old && g < R_old + n) v = chunk[((size_t)u * feat + c) * n + (g - R_old)];
+    else if (g >= 0 && g >= R_old - keep && g < R_old) v = tail_old[((size_t)(g - (R_old - keep)) * U + u) * feat + c];
+    if (j < wn) win[((size_t)u * feat + c) * wn + j] = v;
+    else tail_new[((size_t)(j - wn) * U + u) * feat + c] = v;
+}
+
+hipError_t launch_stream_mel_window(const float *tail_old, const float *chunk, int U, int feat, int n, int R_old,
+                                    int keep, int w0, int wn, float *win, float *tail_new, hipStream_t st) {
+    const int total = U * feat * (wn + keep);
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_mel_window_kernel, dim3((total + 255) / 256), dim3(256), 0, st, tail_old, chunk, U, feat,
+                       n, R_old, keep, w0, wn, win, tail_new);
+    return hipGetLastError();
+}
+
 }  // namespace wrnn

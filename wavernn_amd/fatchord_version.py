@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from . import condition, dsp
-from .loop import LOOP_KEYS, FatchordLoop, noise_width
+from .loop import LOOP_KEYS, FatchordLoop, FatchordStream, noise_width
 
 
 # --------------------------------------------------------------------- upsample network
@@ -219,18 +219,25 @@ class WaveRNN(nn.Module):
         res = self.upsample.resnet
         if os.environ.get("WRNN_TORCH_MELRESNET"):   # A/B: the torch module (MIOpen)
             return res(padded)
+        try:
+            return condition.melresnet(*self._melresnet_packed(), padded)
+        except nat.WrnnError as e:
+            if e.code != -6:   # WRNN_EUNSUPPORTED
+                raise
+            return res(padded)
+
+    @torch.no_grad()
+    def _melresnet_packed(self):
+        """(wrnn_melresnet_cfg, packed weights) of the MelResNet, repacked when its parameters or
+        BatchNorm statistics changed."""
+        res = self.upsample.resnet
         key = tuple((p.data_ptr(), p._version) for p in res.parameters()) + \
             tuple((b.data_ptr(), b._version) for b in res.buffers())
         if getattr(self, "_mr_key", None) != key:
             self._mr_cfg = condition.melresnet_cfg(res)
             self._mr_packed = condition.melresnet_pack(res)
             self._mr_key = key
-        try:
-            return condition.melresnet(self._mr_cfg, self._mr_packed, padded)
-        except nat.WrnnError as e:
-            if e.code != -6:   # WRNN_EUNSUPPORTED
-                raise
-            return res(padded)
+        return self._mr_cfg, self._mr_packed
 
     @torch.no_grad()
     def conditioning(self, mels, batched, target, overlap):
@@ -359,6 +366,44 @@ class WaveRNN(nn.Module):
         self.train()
         return outputs
 
+    # --------------------------------------------------------------------- streaming
+    def stream(self, n_streams: int = 1, total_frames: Optional[int] = None, *, noise=None,
+               seed: Optional[int] = None, row_offset: int = 0) -> "WaveRNNStream":
+        """A streaming session: push mel frames as the acoustic model produces them, get the audio
+        that has become final — unbatched MoL generate() in pieces, the recurrent state kept on the
+        GPU between pushes (C-ABI wrnn_stream_*).  `n_streams` utterances (1..8) advance in lock
+        step.  `total_frames`, when known, lets the session emit up to the fade-out instead of
+        holding back 21 frames.  `noise` [steps][n_streams][11] injects the sampler draws by
+        absolute step; otherwise Philox keyed by `seed` and row_offset + u, the draws generate()
+        takes.  Modes and dims the session kernels do not cover raise NotImplementedError."""
+        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset)
+
+    def generate_stream(self, mels, chunk_frames: int = 8, *, noise=None, seed: Optional[int] = None,
+                        row_offset: int = 0):
+        """generate(mels, None, False, ...) as a generator of float64 chunks, for a mel known up
+        front: mels [1][feat][T] (or [U][feat][T], chunks [U][m]) pushed `chunk_frames` at a time
+        (or by the frame counts of a sequence).  The chunks concatenate to generate()'s output."""
+        device = next(self.parameters()).device
+        mels = torch.as_tensor(mels, device=device).to(torch.float32)
+        if mels.dim() != 3:
+            raise ValueError("mels must be [U][feat][T]")
+        U, _, T = mels.shape
+        counts = [chunk_frames] * (-(-T // chunk_frames)) if isinstance(chunk_frames, int) else list(chunk_frames)
+        if any(c < 1 for c in counts):
+            raise ValueError("chunk_frames must be positive")
+        with self.stream(U, T, noise=noise, seed=seed, row_offset=row_offset) as s:
+            f = 0
+            for c in counts:
+                if f >= T:
+                    break
+                out = s.push(mels[:, :, f:f + c])
+                f = min(T, f + c)
+                if out.shape[1]:
+                    yield out[0] if U == 1 else out
+            out = s.finish()
+            if out.shape[1]:
+                yield out[0] if U == 1 else out
+
     def gen_display(self, i, seq_len, b_size, start):
         gen_rate = (i + 1) / max(time.time() - start, 1e-9) * b_size / 1000
         print(f'| {i + 1}/{seq_len} steps × {b_size} rows | Gen Rate: {gen_rate:.1f}kHz |')
@@ -449,3 +494,45 @@ class WaveRNN(nn.Module):
 
     def noise_width(self) -> int:
         return noise_width(self.mode, self.n_classes)
+
+
+class WaveRNNStream:
+    """The session WaveRNN.stream() returns: push(mel_chunk) → float64 [U][m] (m may be 0),
+    finish() → the tail; a context manager; `lookahead_frames` is how many frames behind the
+    newest one the loop runs (voc_pad + 1)."""
+
+    def __init__(self, model: WaveRNN, n_streams: int, total_frames: Optional[int], noise, seed: Optional[int],
+                 row_offset: int):
+        device = next(model.parameters()).device
+        if device.type != 'cuda':
+            raise RuntimeError("WaveRNN.stream runs on the MI355X HIP path: move the model to a GPU "
+                               "(model.to('cuda')); there is no CPU fallback")
+        self.device = device
+        nz = None
+        if noise is not None:
+            nz = torch.as_tensor(noise, dtype=torch.float32).to(device).contiguous()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        cfg, packed = model._melresnet_packed()
+        self._session = FatchordStream(model.loop_handle(), model._upsample_spec(), cfg, packed, n_streams,
+                                       total_frames, nz, seed, row_offset)
+        self.n_streams = n_streams
+        self.lookahead_frames = self._session.lookahead_frames
+
+    def push(self, mel_chunk) -> np.ndarray:
+        mel = torch.as_tensor(mel_chunk, device=self.device).to(torch.float32)
+        if mel.dim() == 2:
+            mel = mel[None]
+        return self._session.push(mel.contiguous()).cpu().numpy()
+
+    def finish(self) -> np.ndarray:
+        return self._session.push(None, final=True).cpu().numpy()
+
+    def close(self) -> None:
+        self._session.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -1,7 +1,7 @@
 """Vocoder CLI on the MI355X path — the reference's gen_wavernn.py:68-150 flags.
 
     python -m wavernn_amd.gen_wavernn -f mel.npy [-b|-u] [-t T] [-o O] [-w weights.pyt]
-                                      [--hp_file hparams.py] [--out_dir DIR]
+                                      [--hp_file hparams.py] [--out_dir DIR] [--stream-chunk N]
 
 Mel input is a normalised (n_mels, n_hops) .npy in [0, 1] (checked like gen_wavernn.py:48-57).
 The test-set mode and wav input need the training data pipeline / librosa feature
@@ -51,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--hp_file", metavar="FILE", default=None)
     ap.add_argument("--out_dir", default=".")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--stream-chunk", type=int, default=None, metavar="N",
+                    help="unbatched only: vocode through a streaming session, N mel frames per push (same wav)")
     ap.set_defaults(batched=None)
     args = ap.parse_args(argv)
     hp = HParams().configure(args.hp_file)
@@ -67,7 +69,17 @@ def main(argv=None):
     k = model.get_step() // 1000
     tag = f"gen_batched_target{target}_overlap{overlap}" if batched else "gen_NOT_BATCHED"
     out = Path(args.out_dir) / f"__{path.stem}__{k}k_steps_{tag}.wav"
-    model.generate(mel, out, batched, target, overlap, hp.mu_law, seed=args.seed)
+    if args.stream_chunk is not None:
+        if batched:
+            ap.error("--stream-chunk streams the unbatched loop: pass -u")
+        if args.stream_chunk < 1:
+            ap.error("--stream-chunk needs a positive frame count")
+        from . import dsp
+        model.eval()
+        chunks = list(model.generate_stream(mel, args.stream_chunk, seed=args.seed))
+        dsp.save_wav(np.concatenate(chunks), out, hp.sample_rate)
+    else:
+        model.generate(mel, out, batched, target, overlap, hp.mu_law, seed=args.seed)
     print(f"wrote {out}")
 
 

@@ -7,6 +7,7 @@ all L steps for B rows in a single persistent-kernel launch per row chunk.
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import Mapping, Optional, Tuple
 
 import numpy as np
@@ -121,6 +122,7 @@ class FatchordLoop:
 
     def _create(self, cfg, device: int) -> None:
         L = nat.lib()
+        self._sessions = weakref.WeakSet()   # open FatchordStream sessions
         h = ctypes.c_void_p()
         rc = L.wrnn_create(ctypes.byref(cfg), device, ctypes.byref(h))
         self._h = h
@@ -267,9 +269,123 @@ class FatchordLoop:
         return {f: getattr(i, f) for f, _ in nat.Info._fields_}
 
     def close(self) -> None:
+        for s in list(getattr(self, "_sessions", ())):   # a session must not outlive its handle
+            s.close()
         if getattr(self, "_h", None):
             nat.lib().wrnn_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stream_plan(spec, frames_received: int, final: bool = False, total_frames: Optional[int] = None) -> Tuple[int, int]:
+    """(steps_done, audio_done) of a streaming session after `frames_received` mel frames (C-ABI
+    wrnn_stream_plan, host only): the emission rule of include/wavernn_amd.h.  `spec` is the
+    condition.UpsampleSpec (only its scales and pad count).  Raises WrnnError(WRNN_EINVAL) where a
+    push would: final with fewer than 21 frames, or a count other than total_frames."""
+    steps, audio = ctypes.c_int64(), ctypes.c_int64()
+    nat.check_cond(nat.lib().wrnn_stream_plan(ctypes.byref(spec.cfg), frames_received, int(final),
+                                              -1 if total_frames is None else int(total_frames),
+                                              ctypes.byref(steps), ctypes.byref(audio)))
+    return steps.value, audio.value
+
+
+def stream_lookahead(spec) -> int:
+    """Frames a session holds back before it runs a frame's samples (pad + 1)."""
+    n = nat.lib().wrnn_stream_lookahead(ctypes.byref(spec.cfg))
+    if n < 0:
+        nat.check_cond(n)
+    return n
+
+
+class FatchordStream:
+    """A streaming session on a FatchordLoop (C-ABI wrnn_stream_*): `n_streams` utterances in lock
+    step, mel frames pushed as they arrive, float64 audio returned as soon as it is final.  The
+    recurrent state, frame-term stores and mel tail live on the GPU in the session, so one-shot
+    generate() calls and other sessions on the same loop may run between pushes.  Dims or modes
+    the session kernels do not cover raise NotImplementedError with the library's message."""
+
+    def __init__(self, loop: FatchordLoop, spec, mr_cfg, mr_packed: torch.Tensor, n_streams: int = 1,
+                 total_frames: Optional[int] = None, noise: Optional[torch.Tensor] = None, seed: int = 0,
+                 row_offset: int = 0):
+        self._s = None
+        if getattr(loop, "_padded", False):
+            raise NotImplementedError("streaming sessions need rnn / fc / aux dims that are multiples of 4")
+        if noise is not None:
+            if not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()) or \
+                    noise.dim() != 3 or tuple(noise.shape[1:]) != (n_streams, loop.noise_k):
+                raise ValueError(f"noise must be a contiguous fp32 CUDA tensor [steps][{n_streams}][{loop.noise_k}]")
+        if not (mr_packed.is_cuda and mr_packed.dtype == torch.float32 and mr_packed.is_contiguous()):
+            raise ValueError("the packed MelResNet weights must be a contiguous fp32 CUDA tensor")
+        self.loop, self.spec, self.n_streams, self.total_frames = loop, spec, n_streams, total_frames
+        self._keep = (mr_packed, noise, mr_cfg)        # the session reads them until close()
+        self.device = torch.device("cuda", loop.device)
+        self.frames, self.finished = 0, False
+        self.lookahead_frames = stream_lookahead(spec)
+        s = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = nat.lib().wrnn_stream_open(loop._h, ctypes.byref(spec.cfg), ctypes.byref(mr_cfg), mr_packed.data_ptr(),
+                                            n_streams, -1 if total_frames is None else int(total_frames),
+                                            noise.data_ptr() if noise is not None else None,
+                                            noise.shape[0] if noise is not None else 0,
+                                            ctypes.c_uint64(seed & (2 ** 64 - 1)), row_offset, ctypes.byref(s))
+        if rc == -6:   # WRNN_EUNSUPPORTED
+            raise NotImplementedError((nat.lib().wrnn_last_error(loop._h) or b"").decode(errors="replace"))
+        if rc == -1:   # WRNN_EINVAL
+            raise ValueError((nat.lib().wrnn_last_error(loop._h) or b"").decode(errors="replace"))
+        nat.check(loop._h, rc)
+        self._s = s
+        loop._sessions.add(self)
+
+    def plan(self, frames: int, final: bool = False) -> int:
+        """Samples per utterance the session will have emitted in all once `frames` frames are in."""
+        return stream_plan(self.spec, frames, final, self.total_frames)[1]
+
+    def push(self, mel: Optional[torch.Tensor], final: bool = False, stream=None, check: bool = True) -> torch.Tensor:
+        """mel [U][feat][n] fp32 on the loop's GPU (None: no frames) → the new audio, float64 [U][m]
+        on the GPU (m may be 0).  Asynchronous on `stream` when check=False."""
+        if self._s is None:
+            raise RuntimeError("the session is closed")
+        if self.finished:
+            raise RuntimeError("push after finish(): the session has ended")
+        n = 0
+        if mel is not None:
+            if not (mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3) or \
+                    tuple(mel.shape[:2]) != (self.n_streams, self.loop.feat_dims):
+                raise ValueError(f"mel must be a contiguous fp32 CUDA tensor [{self.n_streams}][{self.loop.feat_dims}][n]")
+            n = mel.shape[2]
+        try:
+            m = self.plan(self.frames + n, final) - self.plan(self.frames)
+        except nat.WrnnError as e:
+            raise ValueError(str(e)) from None
+        wave = torch.empty(self.n_streams, m, dtype=torch.float64, device=self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        got = ctypes.c_int()
+        rc = nat.lib().wrnn_stream_push(self._s, mel.data_ptr() if n else None, n, int(final),
+                                        wave.data_ptr() if m else None, m, ctypes.byref(got), stream)
+        nat.check(self.loop._h, rc)
+        assert got.value == m, (got.value, m)
+        self.frames += n
+        self.finished = bool(final)
+        if check:
+            self.loop.check(stream)
+        return wave
+
+    def close(self) -> None:
+        if getattr(self, "_s", None) is not None:
+            nat.lib().wrnn_stream_close(self._s)
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
