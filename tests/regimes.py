@@ -297,3 +297,82 @@ def generate_inputs(batched: bool, seed: int = STATE_SEED):
     for a in (mel, noise, ref):
         a.setflags(write=False)
     return d, state, mel, noise, ref
+
+
+# ------------------------------------------------------------------- streaming sessions
+# Inputs of tests/test_gpu_streaming_shapes.py: a model at one of the geometries of
+# tests/geometries.py, mels for U utterances, injected draws by absolute step, and what
+# oracle.generate (unbatched) makes of each utterance alone with its own column of the draws.
+STREAM_MODELS = {
+    # name: (rnn dims, GRU gain of hot_fatchord_state or None for the standard narrow state, sparsity)
+    "std512": (512, None, None),
+    "stdsparse896": (896, None, 0.95),
+    "mol512": (512, MODELS["mol512"][1], None),
+    "sparse896": (896, MODELS["sparse896"][1], MODELS["sparse896"][2]),
+}
+STREAM_STD_SEED = 3        # geometries.TAP_SEED: the states tests/test_gpu_frame_geometry.py runs
+# The hot sessions (CPU conditions: tests/test_regimes.py): (model, geometry, U, frames, state seed).
+# Dense: 2 × 24 × 12 = 576 row-steps; sparse: 2 × 30 × 12 = 720 (≤ 800 at rnn 896).
+STREAM_HOT_DENSE = ("mol512", "hop12", 2, 24, STATE_SEED)
+STREAM_HOT_SPARSE = ("sparse896", "hop12", 2, 30, 12)
+STREAM_HOT_275 = ("mol512", "hop275", 1, GEN_FRAMES, STATE_SEED)      # generate_inputs(False)
+STREAM_HOT = [STREAM_HOT_DENSE, STREAM_HOT_SPARSE]
+
+
+@dataclass(frozen=True)
+class StreamInput:
+    dims: syn.FatchordDims
+    state: Dict[str, np.ndarray]
+    mels: np.ndarray      # [U][feat][T]
+    noise: np.ndarray     # [T·hop][U][11]
+    ref: np.ndarray       # [U][(T − 1)·hop] float64, oracle.generate per utterance
+
+
+def upsample_spec(d: syn.FatchordDims, state):
+    from wavernn_amd import condition
+    taps = [state[f"upsample.up_layers.{2 * i + 1}.weight"] for i in range(len(d.upsample_factors))]
+    return condition.UpsampleSpec(d.feat_dims, d.res_out_dims, d.pad, d.upsample_factors, taps)
+
+
+@functools.lru_cache(maxsize=None)
+def stream_inputs(model: str, geom: str, n_utt: int, frames: int, seed: int) -> StreamInput:
+    """A streaming case's inputs and expectation; computed once per process and shared (read-only).
+    ("mol512", "hop275", 1, 24, seed) is generate_inputs(False, seed), so its oracle run is shared
+    with tests/test_gpu_regimes.py."""
+    from oracle import oracle
+    from tests import geometries as geo
+    from wavernn_amd import condition
+    if geom == "hop275":
+        assert (model, n_utt, frames) == STREAM_HOT_275[:1] + STREAM_HOT_275[2:4]
+        d, state, mel, noise, ref = generate_inputs(False, seed)
+        mels, ref = mel[None], ref[None]
+    else:
+        rnn, gain, sparsity = STREAM_MODELS[model]
+        d = geo.geom_dims(geom, rnn_dims=rnn)
+        if gain is None:
+            state = syn.make_fatchord_state(d, seed)
+            if sparsity is not None:
+                state = {k: np.array(v, copy=True) for k, v in prune_state(state, sparsity).items()}
+        else:
+            state = hot_fatchord_state(d, seed, gain, sparsity=sparsity)
+        geo.perturb_taps(state, d, seed)
+        mels = np.stack([syn.make_mel(d.feat_dims, frames, 1000 * seed + 40 + i) for i in range(n_utt)])
+        noise = syn.make_noise(d.mode, n_utt, frames * d.hop_length, d.n_classes, 1000 * seed + 21)
+        ref = np.stack([oracle.generate(state, d, mels[u], False, 0, 0, False, np.ascontiguousarray(noise[:, u:u + 1]))
+                        for u in range(n_utt)])
+    assert condition.frame_weights(upsample_spec(d, state))[:2] == geo.GEOMS[geom][3:5], geom
+    assert ref.shape == (n_utt, (frames - 1) * d.hop_length) and ref.dtype == np.float64
+    for a in (mels, noise, ref):
+        a.setflags(write=False)
+    return StreamInput(d, state, mels, noise, ref)
+
+
+def stream_clamps(ref: np.ndarray, hop: int):
+    """(x = +1, x = −1) per audio position of oracle.generate's output [..][(T − 1)·hop].  Its post
+    multiplies the float64 copy of the last 20·hop loop samples by linspace(1, 0, 20·hop), and a
+    product with ±1 is exact, so a clamped sample is ± that envelope and nothing else is (an
+    unclamped fp32 sample times the envelope does not land on the envelope).  The last position,
+    where the envelope is 0, is left out: every position kept is followed by another loop step."""
+    env = np.ones(ref.shape[-1])
+    env[-20 * hop:] = np.linspace(1, 0, 20 * hop)
+    return (ref == env)[..., :-1], (ref == -env)[..., :-1]

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import oracle as orc
+from tests.geometries import GEOMS, N_TERMS, ODD, TAP_SEED, dims as _dims, perturb_taps, terms_budget_mb
 from tests.golden import fixtures as gf
 
 from wavernn_amd import _native as nat
@@ -27,37 +28,11 @@ from wavernn_amd import synthetic as syn
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 
-# name: (feat, factors, pad, jlo, nJ, frames unbatched, (frames, target, overlap) fold-batched,
-#        steps per chunk)
-GEOMS = {
-    # hop 12 < 32 steps per workgroup, odd feat (terms-GEMM depth 30 + 128 + 4 = 162); E = 16 < 36
-    "hop12": (30, (3, 4), 3, -2, 5, 24, (60, 150, 20), 77),
-    # pad·hop = 4 = E, the exactness boundary; 3 frame weights
-    "hop4": (20, (4,), 1, -1, 3, 24, (24, 20, 4), 37),
-    # pad·hop = 6 = E; 7 frame weights; 16 frames per workgroup
-    "hop2": (80, (1, 1, 2), 3, -3, 7, 24, (24, 10, 2), 13),
-    # four stages; E = 16 + 8 + 4 + 2 = 30 < 32
-    "hop16": (80, (2, 2, 2, 2), 2, -2, 5, 21, (21, 70, 10), 101),
-    # the reference's own geometry (chunked only: its other cases are tests/test_gpu_frame_terms.py)
-    "hop275": (80, (5, 5, 11), 2, -2, 5, 21, None, 1801),
-}
-ODD = [g for g in GEOMS if g != "hop275"]
-N_TERMS = 32 * 160            # kXcdWgs · kXTerms floats per row and step (csrc/fatchord_xcd.h)
-
-
-def _dims(feat, factors, pad):
-    return syn.FatchordDims(feat_dims=feat, upsample_factors=tuple(factors), hop_length=int(np.prod(factors)),
-                            pad=pad, compute_dims=16, res_blocks=1)
-
 
 def _build(d, seed):
     """(state with the box taps perturbed by factors in [0.5, 1.5] so tap order matters, model)."""
     from wavernn_amd.fatchord_version import WaveRNN
-    state = syn.make_fatchord_state(d, seed)
-    rng = np.random.default_rng(100 + seed)
-    for i in range(len(d.upsample_factors)):
-        k = f"upsample.up_layers.{2 * i + 1}.weight"
-        state[k] = (np.asarray(state[k]) * rng.uniform(0.5, 1.5, np.shape(state[k]))).astype(np.float32)
+    state = perturb_taps(syn.make_fatchord_state(d, seed), d, seed)
     m = WaveRNN(**d.ctor_kwargs()).to(DEV)
     m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in state.items()})
     return state, m.eval()
@@ -67,7 +42,7 @@ def _build(d, seed):
 def _geom(name):
     feat, factors, pad, jlo, nJ = GEOMS[name][:5]
     d = _dims(feat, factors, pad)
-    state, m = _build(d, 3)
+    state, m = _build(d, TAP_SEED)
     assert condition.frame_weights(m._upsample_spec())[:2] == (jlo, nJ)
     return d, state, m
 
@@ -185,8 +160,7 @@ def test_time_chunked_launches(name, monkeypatch):
     _env(monkeypatch)
     spec, loop = m._upsample_spec(), m.loop_handle()
     whole, _ = loop.generate_frames(spec, mel_f, aux, 0, 0, seed=13)
-    mb = (X + 1.5) * n_utt * (N_TERMS + d.feat_dims + 128 + 4) * 4 / 2 ** 20
-    _env(monkeypatch, repr(mb))
+    _env(monkeypatch, terms_budget_mb(X, n_utt, N_TERMS + d.feat_dims + 128 + 4))
     _vs_oracle(m, mel_f, aux, 0, 0, noise, ref, f"{name}, chunks of {X} steps")
     chunked, _ = loop.generate_frames(spec, mel_f, aux, 0, 0, seed=13)
     assert loop.info["last_path"] == 5

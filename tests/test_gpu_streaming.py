@@ -55,22 +55,32 @@ def _close(got, ref, what):
     assert diff.max() <= gf.MOL_TOL, f"{what}: max |Δ| {diff.max():.3g}, first over at {np.argwhere(diff > gf.MOL_TOL)[0]}"
 
 
-def _run_session(model, mel, pushes, total, noise=None, **kw):
-    """Push `mel` [U][feat][T] by the frame counts `pushes`, then finish(): (chunks, last_path)."""
+def _run_session(model, mel, pushes, total, noise=None, final_last=False, **kw):
+    """Push `mel` [U][feat][T] by the frame counts `pushes`, then finish(): (chunks, last_path).
+    A count of None is a push without a mel (the C-ABI's n = 0, mel = NULL).  `final_last`: the
+    last count's frames go in the final call itself (push(mel, final=True) of the loop-level
+    session; the model-level wrapper always ends with an empty finish())."""
     spec = model._upsample_spec()
     chunks, f = [], 0
     with model.stream(mel.shape[0], total, noise=noise, **kw) as s:
         assert s.lookahead_frames == model.pad + 1
-        for n in pushes:
-            out = s.push(mel[:, :, f:f + n])
+        for i, n in enumerate(pushes):
+            last = final_last and i == len(pushes) - 1
+            if n is None:
+                n, out = 0, s._session.push(None).cpu().numpy()
+            elif last:
+                out = s._session.push(torch.from_numpy(mel[:, :, f:f + n].copy()).to(s.device), final=True).cpu().numpy()
+            else:
+                out = s.push(mel[:, :, f:f + n])
             f += n
-            want = stream_plan(spec, f, False, total)[1] - stream_plan(spec, f - n, False, total)[1]
+            want = stream_plan(spec, f, last, total)[1] - stream_plan(spec, f - n, False, total)[1]
             assert out.dtype == np.float64 and out.shape == (mel.shape[0], want), (f, out.shape, want)
             chunks.append(out)
         assert f == mel.shape[2]
-        out = s.finish()
-        assert out.shape == (mel.shape[0], stream_plan(spec, f, True, total)[1] - stream_plan(spec, f, False, total)[1])
-        chunks.append(out)
+        if not final_last:
+            out = s.finish()
+            assert out.shape == (mel.shape[0], stream_plan(spec, f, True, total)[1] - stream_plan(spec, f, False, total)[1])
+            chunks.append(out)
         with pytest.raises(RuntimeError):
             s.push(mel[:, :, :1])
     return chunks, model.loop_handle().info["last_path"]

@@ -179,6 +179,61 @@ def test_generate_references_agree(batched):
     assert np.mean(out == 1.0) >= 0.03 and np.mean(out == -1.0) >= 0.03
 
 
+def _stream_param(key):
+    from tests import geometries as geo
+    model, geom, n_utt, frames, seed = key
+    row_steps = n_utt * frames * geo.geom_dims(geom).hop_length
+    return pytest.param(key, id=f"{model}-{geom}-{n_utt}x{frames}",
+                        marks=[pytest.mark.slow] if row_steps >= SLOW_ROW_STEPS else [])
+
+
+@pytest.mark.parametrize("key", [_stream_param(k) for k in rg.STREAM_HOT])
+def test_stream_hot_inputs_agree_and_reach_both_clamps(key):
+    """The hot streaming inputs of tests/test_gpu_streaming_shapes.py (the hop-275 one is
+    generate_inputs(False): test_generate_references_agree[unbatched]).  Per utterance,
+    torch_cpu.timed_generate against the oracle.generate output the GPU tests expect; over the whole
+    input, the loop output at x = +1 and x = −1 on >= 3 % of row-steps each (every input here has at
+    least FULL_ROW_STEPS), and regimes.stream_clamps reads the same events off the oracle's audio.
+    Seeds: dense hop12 state seed 7 (pair 8.3e-7, x=+1 0.035, x=−1 0.104), sparse hop12 state seed
+    12 (pair 6.6e-7, x=+1 0.110, x=−1 0.326): the first seed tried met every condition."""
+    inp = rg.stream_inputs(*key)
+    d, n_utt = inp.dims, key[2]
+    outs, pair = [], 0.0
+    for u in range(n_utt):
+        r = torch_cpu.timed_generate(inp.state, d, inp.mels[u].copy(), False, 0, 0, False,
+                                     np.ascontiguousarray(inp.noise[:, u:u + 1]))
+        assert r["rows"] == 1 and r["wave"].shape == inp.ref[u].shape
+        pair = max(pair, float(np.abs(r["wave"] - inp.ref[u]).max()))
+        outs.append(r["out"])
+    out = np.concatenate(outs, 0)
+    hi, lo = float(np.mean(out == 1.0)), float(np.mean(out == -1.0))
+    print(f"stream {key}: {out.shape[0]} rows x {out.shape[1]} steps, max |Δ| {pair:.3g}, x=+1 {hi:.3f}, x=-1 {lo:.3f}")
+    assert pair <= GEN_PAIR_TOL
+    if out.size >= FULL_ROW_STEPS:
+        assert hi >= 0.03 and lo >= 0.03
+    else:
+        assert hi > 0 and lo > 0
+    # the events as the GPU tests read them off the oracle's audio: the same steps, the fade included
+    pos, neg = rg.stream_clamps(inp.ref, d.hop_length)
+    n = pos.shape[1]
+    assert np.array_equal(pos, out[:, :n] == 1.0) and np.array_equal(neg, out[:, :n] == -1.0)
+    assert pos.any() and neg.any()
+
+
+def test_stream_inputs_follow_the_geometry_table():
+    """Every geometry's standard input: the frame weights the table states (asserted inside
+    stream_inputs on the state the GPU sees), one expectation per utterance, different utterances."""
+    from tests import geometries as geo
+    for geom in geo.ODD:
+        inp = rg.stream_inputs("std512", geom, 3, 24, rg.STREAM_STD_SEED)
+        d = inp.dims
+        assert (d.feat_dims, d.upsample_factors, d.pad) == geo.GEOMS[geom][:3] and d.rnn_dims == 512
+        assert inp.mels.shape == (3, d.feat_dims, 24) and inp.noise.shape == (24 * d.hop_length, 3, 11)
+        assert inp.ref.shape == (3, 23 * d.hop_length) and np.isfinite(inp.ref).all()
+        assert np.abs(inp.ref[0] - inp.ref[1]).max() > 1e-3 and np.abs(inp.ref[1] - inp.ref[2]).max() > 1e-3
+        assert np.abs(inp.ref).max() < 1.0            # the narrow regime: the hot inputs are the others
+
+
 def test_oracle_build_follows_its_source(tmp_path, monkeypatch):
     """oracle.build() rebuilds when the recorded digest differs from the source's (a stale library
     with the old orc_fatchord_loop signature would be called with one argument too many), and not
