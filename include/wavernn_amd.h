@@ -312,6 +312,44 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
 int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, double *wave, int cap, int *n_out,
                      void *stream);
 
+/* Advance `count` sessions of ONE handle, each by its own frames, as wrnn_stream_push would one
+ * after another on `stream` — but with one persistent launch per time chunk for all of them
+ * (group-push addition, same ABI).  A session's utterances advance in lock step: the same frames in
+ * the same push, one total_frames, one end.  A group lifts that between sessions: requests that
+ * arrived at different times, have different lengths and receive frames at different moments share
+ * the GPU, each row on its own XCD over its own step window.
+ *   sessions [count]  members: sessions of any U on the same handle (and so the same loop kernel),
+ *                     their rows together <= 8, none listed twice, none NULL
+ *   mel      [count]  member i's [U_i][feat_dims][n_i] (device), or NULL where n_i = 0 (the array
+ *                     itself may be NULL when every n_i = 0)
+ *   n, final [count]  as wrnn_stream_push, per member: different totals, different frames received
+ *                     so far and different final flags are the normal case
+ *   wave, cap, n_out [count]  member i's [U_i][cap_i] float64 (device) and its sample count
+ * For every member the result is what wrnn_stream_push(sessions[i], mel[i], n[i], final[i],
+ * wave[i], cap[i], &n_out[i], stream) produces: the same emission rule, the same n_out, the same
+ * samples.  Each member's conditioning (mel window, MelResNet, frame-term rows, the terms of its
+ * steps) runs as in a single push; then launch round j runs time chunk j of every member that
+ * still has one, member i's rows on the XCDs after those of the members before it.  The grouped
+ * instantiation of the kernel runs the same arithmetic per row in the same order, no hand-off
+ * crosses XCDs, so the audio is bit-identical to the session pushed alone on the same schedule.
+ * A member whose push makes no step runnable (n = 0, or still inside its look-ahead) takes no XCD;
+ * if no member has a step to run no persistent launch is queued, the conditioning and post work of
+ * each member still happens.  The WRNN_TERMS_MB budget is shared by all rows with steps to run:
+ * a round takes floor(budget / (rows * N) - 1) steps of each, members with fewer steps drop out of
+ * the later rounds.
+ * Arguments are checked for EVERY member before anything is queued for any of them: count >= 1,
+ * the entries above, and per member the checks of wrnn_stream_push (counts against the emission
+ * rule, cap, injected draws long enough, not dead, not finished).  On WRNN_EINVAL (message in
+ * wrnn_last_error, prefixed "member i: " for a member's own check) every member is unchanged and
+ * usable, every n_out is 0.  A failure after queuing has begun kills every member of the group, as
+ * a failed single push kills its session.
+ * Ordering as wrnn_stream_open states: one stream per handle; one-shot calls, single pushes and
+ * other group pushes may run between two group pushes in stream order.  Sets wrnn_info.last_path
+ * (5 or 6) when a persistent launch was queued and leaves wrnn_elapsed_ms alone.  Asynchronous
+ * except where a member's workspace must grow, as wrnn_stream_push. */
+int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const float *const *mel, const int *n,
+                           const int *final, double *const *wave, const int *cap, int *n_out, void *stream);
+
 /* The emission rule as a function (host only, stateless): the counts a session reports after
  * frames_received frames (`final`: they were the last), total_frames as given to open (−1: unknown).
  * Only ucfg's scales and pad are read.  WRNN_EINVAL as wrnn_stream_push. */

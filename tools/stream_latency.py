@@ -2,7 +2,7 @@
 """First-audio latency and total time of streamed synthesis on the headline model (MoL rnn/fc 512,
 401 frames = 5 s), against the one-shot generate() of the same process.
 
-    python tools/stream_latency.py [--chunks 4 8 32] [--reps 5] [--frames 401]
+    python tools/stream_latency.py [--chunks 4 8 32] [--reps 5] [--frames 401] [--independent 8]
 
 Per chunk size c (mel frames per push), total_frames announced (no 21-frame hold-back) and not:
   (a) first audio: the push that brings the session to the first frame count at which c frames of
@@ -12,6 +12,16 @@ Per chunk size c (mel frames per push), total_frames announced (no 21-frame hold
   (b) total: all 401 frames pushed c at a time, every push's audio copied to the host — host time
       from the first push to the last sample on the host, device time likewise, and the number of
       pushes that launched the persistent kernel.
+--independent N (default 8; 0 skips it) adds the server case, per chunk size c: N single-utterance
+Philox sessions with lengths spread from 201 to 401 frames, session i opening 4·i ticks after
+session 0, every open session pushing c frames per tick — run (a) with one wrnn_stream_push per
+session per tick (one persistent launch each, one XCD busy) and (b) with one group push per tick
+(wrnn_stream_push_group: one launch, a row per XCD).  Reported: wall time per tick (call to device
+idle), aggregate samples/s and × real time, persistent launches, and the host time of a tick's
+asynchronous call(s) — the per-member conditioning, the launch and the post being queued, an upper
+bound of the host time before the persistent launch.  (a) and (b) must produce identical audio.
+Beside it, on N mels of 401 frames from tick 0: a lock-step U = N session (the windowed kernel)
+against a group of N U = 1 sessions (the grouped kernel), wall µs per step of a row.
 Every shape is warmed by one untimed session first (code objects, rocBLAS algorithm choice); each
 figure is the median of --reps fresh sessions (a session allocates its workspaces in its first
 pushes: that is part of what a caller waits for, and it is included).  One JSON line per row."""
@@ -74,12 +84,114 @@ def total(model, mel, c, known, dev):
     return host, devms, launches
 
 
+def _ticks(model, mels, starts, c, grouped, dev, n_streams=1):
+    """Sessions over `mels` ([U][feat][T_i] each), session i opening at tick starts[i], c frames per
+    tick and an empty final push after the last: per tick one push per open session, or one group
+    push.  → (audio per session, wall ms per tick, host ms per tick in the asynchronous calls,
+    persistent launches, wall ms in all)."""
+    spec, loop = model._upsample_spec(), model.loop_handle()
+    N = len(mels)
+    sess, f, out = [None] * N, [0] * N, [[] for _ in range(N)]
+    walls, hosts, launches = [], [], 0
+    torch.cuda.synchronize(dev)
+    t_begin = time.perf_counter()
+    try:
+        tick = 0
+        while any(s is None or not s._session.finished for s in sess):
+            for i in range(N):   # opening a session synchronises: outside the tick's clock
+                if sess[i] is None and tick >= starts[i]:
+                    sess[i] = model.stream(n_streams, mels[i].shape[2], seed=1000, row_offset=i * n_streams)
+            live = [i for i in range(N) if sess[i] is not None and not sess[i]._session.finished]
+            pushes, ran = [], 0
+            for i in live:
+                T = mels[i].shape[2]
+                n = min(c, T - f[i])
+                before = stream_plan(spec, f[i], False, T)[0]
+                ran += stream_plan(spec, f[i] + n, n == 0, T)[0] > before
+                pushes.append((sess[i]._session, mels[i][:, :, f[i]:f[i] + n].contiguous() if n else None, n == 0))
+                f[i] += n
+            launches += (ran > 0) if grouped else ran
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            if grouped:
+                got = loop.push_streams(pushes, check=False) if pushes else []
+            else:
+                got = [s.push(mel, final=final, check=False) for s, mel, final in pushes]
+            t1 = time.perf_counter()
+            torch.cuda.synchronize(dev)
+            t2 = time.perf_counter()
+            if pushes:
+                walls.append((t2 - t0) * 1e3)
+                hosts.append((t1 - t0) * 1e3)
+            for i, w in zip(live, got):
+                out[i].append(w)
+            tick += 1
+        loop.check()
+    finally:
+        for s in sess:
+            if s is not None:
+                s.close()
+    total_ms = (time.perf_counter() - t_begin) * 1e3
+    return [torch.cat(o, 1).cpu().numpy() for o in out], walls, hosts, launches, total_ms
+
+
+def independent(model, N, c, reps, dev, d):
+    """The server case and the lock-step comparison (module docstring), one JSON line each."""
+    med = statistics.median
+    lengths = [401 if N == 1 else 201 + round(i * 200 / (N - 1)) for i in range(N)]
+    mels = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=10 + i))[None].to(dev) for i, T in enumerate(lengths)]
+    starts = [4 * i for i in range(N)]
+    samples = sum((T - 1) * d.hop_length for T in lengths)
+    rows = {}
+    for grouped in (False, True):
+        _ticks(model, mels, starts, c, grouped, dev)
+        runs = [_ticks(model, mels, starts, c, grouped, dev) for _ in range(reps)]
+        rows[grouped] = runs
+        if grouped:
+            for a, b in zip(rows[False][0][0], runs[0][0]):
+                assert np.array_equal(a, b), "group pushes and single pushes produced different audio"
+        busy = med(sum(r[1]) for r in runs)   # the ticks alone: opening a session synchronises and is left out
+        print(json.dumps({
+            "what": "independent sessions, " + ("one group push per tick" if grouped else "one push per session per tick"),
+            "sessions": N, "frames": lengths, "chunk_frames": c, "ticks": len(runs[0][1]),
+            "tick_wall_ms_median": round(med(med(r[1]) for r in runs), 3),
+            "tick_wall_ms_max": round(med(max(r[1]) for r in runs), 3),
+            "tick_host_queue_ms_median": round(med(med(r[2]) for r in runs), 3),
+            "persistent_launches": runs[0][3], "busy_ms": round(busy, 2),
+            "samples_per_s": round(samples / busy * 1e3), "x_real_time": round(samples / d.sample_rate / busy * 1e3, 2),
+            "reps": reps}), flush=True)
+    # lock step against a group, the same N mels of 401 frames from tick 0
+    T = 401
+    same = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=10 + i))[None].to(dev) for i in range(N)]
+    steps = T * d.hop_length
+    cases = (("lock-step U = %d session (windowed kernel)" % N, [torch.cat(same, 0)], False, N),
+             ("group of %d U = 1 sessions (grouped kernel)" % N, same, True, 1))
+    audio = {}
+    for what, ms, grouped, U in cases:
+        _ticks(model, ms, [0] * len(ms), c, grouped, dev, n_streams=U)
+        runs = [_ticks(model, ms, [0] * len(ms), c, grouped, dev, n_streams=U) for _ in range(reps)]
+        audio[grouped] = np.concatenate(runs[0][0], 0)
+        busy = [sum(r[1]) for r in runs]
+        print(json.dumps({
+            "what": what, "rows": N, "frames": T, "chunk_frames": c, "persistent_launches": runs[0][3],
+            "busy_ms": round(med(busy), 2), "busy_ms_min_max": [round(min(busy), 2), round(max(busy), 2)],
+            "wall_us_per_step": round(med(busy) * 1e3 / steps, 4),
+            "tick_host_queue_ms_median": round(med(med(r[2]) for r in runs), 3),
+            "x_real_time": round(N * (T - 1) * d.hop_length / d.sample_rate / med(busy) * 1e3, 2), "reps": reps}), flush=True)
+    assert np.array_equal(audio[False], audio[True]), "the lock-step session and the group produced different audio"
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--chunks", type=int, nargs="+", default=[4, 8, 32])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--frames", type=int, default=401)
+    ap.add_argument("--independent", type=int, default=8, metavar="N",
+                    help="sessions of the server case (1..8; 0: skip it)")
+    ap.add_argument("--only-independent", action="store_true", help="skip the single-session latency rows")
     args = ap.parse_args()
+    if not 0 <= args.independent <= 8:
+        ap.error("--independent takes 0..8 sessions (a group has at most 8 rows)")
     if not torch.cuda.is_available():
         sys.exit("stream_latency.py times the GPU path: no GPU visible")
     dev = torch.device("cuda", 0)
@@ -98,7 +210,7 @@ def main():
     print(json.dumps({"what": "one-shot generate()", "frames": args.frames, "host_ms": round(base_host, 3),
                       "device_ms": round(base_dev, 3), "loop_kernel_ms": round(model.loop_handle().elapsed_ms(), 3),
                       "reps": args.reps}), flush=True)
-    for known in (True, False):
+    for known in (() if args.only_independent else (True, False)):
         for c in args.chunks:
             first_audio(model, mel, c, known, dev)
             fa = [first_audio(model, mel, c, known, dev) for _ in range(args.reps)]
@@ -115,6 +227,9 @@ def main():
                 "total_host_ms": round(host, 3), "total_device_ms": round(med(t[1] for t in tt), 3),
                 "launches": launches, "one_shot_host_ms": round(base_host, 3),
                 "per_relaunch_overhead_ms": round((host - base_host) / launches, 4), "reps": args.reps}), flush=True)
+    if args.independent:
+        for c in args.chunks:
+            independent(model, args.independent, c, args.reps, dev, d)
     model.train()
 
 

@@ -21,7 +21,7 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_postprocess", "wrnn_cond_last_error", "wrnn_generate_frames", "wrnn_generate_frames_rows",
            "wrnn_frame_weights", "wrnn_melresnet_floats", "wrnn_melresnet", "wrnn_philox_draws",
            "wrnn_melresnet_tile_frames", "wrnn_stream_open", "wrnn_stream_push", "wrnn_stream_plan",
-           "wrnn_stream_lookahead", "wrnn_stream_close")
+           "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -114,6 +114,9 @@ def lib() -> ctypes.CDLL:
     L.wrnn_stream_open.restype = i32
     L.wrnn_stream_push.argtypes = [vp, vp, i32, i32, vp, i32, pi, vp]
     L.wrnn_stream_push.restype = i32
+    # arrays of `count` entries: sessions, mel pointers, n, final, wave pointers, cap, n_out
+    L.wrnn_stream_push_group.argtypes = [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), pi, pi, ctypes.POINTER(vp), pi, pi, vp]
+    L.wrnn_stream_push_group.restype = i32
     L.wrnn_stream_plan.argtypes = [ctypes.POINTER(UpsampleCfg), i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.wrnn_stream_plan.restype = i32
     L.wrnn_stream_lookahead.argtypes = [ctypes.POINTER(UpsampleCfg)]

@@ -53,9 +53,11 @@ hipError_t prepare_split_kernel(int max_lds_bytes);
 hipError_t split_occupancy(int *blocks_per_cu, size_t lds_bytes);
 bool split_has_kernel(int R, int F);
 hipError_t launch_xcd(const XcdArgs &a, hipStream_t st);
+hipError_t launch_xcd_group(const XcdGroupArgs &g, hipStream_t st);
 hipError_t prepare_xcd_kernel(int max_lds_bytes);
 hipError_t xcd_occupancy(int *blocks_per_cu);
 hipError_t launch_xcds(const XcdsArgs &a, hipStream_t st);
+hipError_t launch_xcds_group(const XcdsGroupArgs &g, hipStream_t st);
 hipError_t prepare_xcds_kernel(int max_lds_bytes);
 hipError_t xcds_occupancy(int *blocks_per_cu);
 hipError_t launch_xcdm(const XcdmArgs &a, int nq, bool raw, hipStream_t st);
@@ -2806,22 +2808,47 @@ static int stream_launches(wrnn_stream *s, int t_begin, int t_end, bool last, co
 }
 }  // extern "C++"
 
-static int stream_push(wrnn_stream *s, const float *mel, int n, bool final, double *wave, int cap, int *n_out,
-                       hipStream_t st) {
+// One member's share of a push (wrnn_stream_push: the group of one), in three parts: the argument
+// checks (stream_check: nothing queued, nothing changed), the conditioning of the new frames and the
+// sample window of the steps that became runnable (stream_prepare), then — after the persistent
+// launch(es) of those steps — the float64 post and the counters (stream_finish).
+struct StreamPush {
+    const float *mel = nullptr;
+    int n = 0;
+    bool final = false;
+    double *wave = nullptr;
+    int cap = 0;
+    long long S_new = 0, Au_new = 0;   // the counts after this push
+    int S_old = 0, m = 0, R_new = 0, A_new = 0;
+};
+
+static int stream_check(wrnn_stream *s, StreamPush &p) {
+    wrnn_t *h = s->h;
+    if (s->dead) return fail(h, WRNN_EINVAL, "the session failed in an earlier push: close it");
+    if (s->fin) return fail(h, WRNN_EINVAL, "push after the final one: the session is finished");
+    if (p.n < 0 || (p.n > 0 && !p.mel) || p.cap < 0) return fail(h, WRNN_EINVAL, "need n >= 0, mel when n > 0, cap >= 0");
+    std::string msg;
+    if (int rc = stream_counts(s->hop, s->pad + 1, (long long)s->R + p.n, p.final, s->T_known, &p.S_new, &p.Au_new, &msg))
+        return fail(h, rc, msg);
+    p.m = (int)(p.Au_new - s->audio);
+    if (p.m > 0 && (!p.wave || p.cap < p.m))
+        return fail(h, WRNN_EINVAL, "this push emits " + std::to_string(p.m) + " samples per utterance: wave holds " +
+                                        std::to_string(p.wave ? p.cap : 0));
+    if (s->noise && p.S_new > s->noise_steps)
+        return fail(h, WRNN_EINVAL, "the injected draws cover " + std::to_string(s->noise_steps) + " steps, the loop reaches " +
+                                        std::to_string(p.S_new));
+    p.S_old = s->steps;
+    return WRNN_OK;
+}
+
+static int stream_prepare(wrnn_stream *s, StreamPush &p, hipStream_t st) {
     wrnn_t *h = s->h;
     const int U = s->U, feat = h->cfg.feat_dims, A4 = h->CD - feat, KX = h->KXc, N = s->N, pad = s->pad;
     const int jhi = s->jlo + s->nJ - 1;
-    long long S_new = 0, Au_new = 0;
-    std::string msg;
-    if (int rc = stream_counts(s->hop, pad + 1, (long long)s->R + n, final, s->T_known, &S_new, &Au_new, &msg))
-        return fail(h, rc, msg);
-    const int m = (int)(Au_new - s->audio);
-    if (m > 0 && (!wave || cap < m))
-        return fail(h, WRNN_EINVAL, "this push emits " + std::to_string(m) + " samples per utterance: wave holds " +
-                                        std::to_string(wave ? cap : 0));
-    if (s->noise && S_new > s->noise_steps)
-        return fail(h, WRNN_EINVAL, "the injected draws cover " + std::to_string(s->noise_steps) + " steps, the loop reaches " +
-                                        std::to_string(S_new));
+    const float *mel = p.mel;
+    const int n = p.n;
+    const bool final = p.final;
+    const long long S_new = p.S_new;
     // From here on work is queued and the session's stores advance: a failure on the way, whatever
     // its code, leaves them out of step with the frame counts, so the session is dead until the end
     s->dead = true;
@@ -2897,37 +2924,168 @@ static int stream_push(wrnn_stream *s, const float *mel, int n, bool final, doub
             s->y_cur = o;
             s->y_t0 = s->audio;
         }
-        HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
-        h->last_path = (int)s->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
-        int rc;
-        if (s->path == P_XCD) rc = stream_launches<XcdArgs>(s, S_old, (int)S_new, final, h->xs, launch_xcd, st);
-        else rc = stream_launches<XcdsArgs>(s, S_old, (int)S_new, final, h->xss, launch_xcds, st);
-        if (rc) return rc;
     }
-    if (m > 0) {
-        const int T = final ? R_new : s->T_known;
-        HIP_TRY(h, launch_postprocess_stream(s->d_y[s->y_cur], U, s->y_ld[s->y_cur], s->y_t0, s->audio, m,
-                                             T >= 0 ? (T - 1) * s->hop : -1, 20 * s->hop, wave, cap, st));
-    }
-    s->R = R_new;
-    s->A = A_new;
-    s->steps = (int)S_new;
-    s->audio = (int)Au_new;
-    s->fin = final;
-    s->dead = false;
-    if (n_out) *n_out = m;
+    p.R_new = R_new;
+    p.A_new = A_new;
     return WRNN_OK;
 }
 
+static int stream_finish(wrnn_stream *s, const StreamPush &p, int *n_out, hipStream_t st) {
+    wrnn_t *h = s->h;
+    if (p.m > 0) {
+        const int T = p.final ? p.R_new : s->T_known;
+        HIP_TRY(h, launch_postprocess_stream(s->d_y[s->y_cur], s->U, s->y_ld[s->y_cur], s->y_t0, s->audio, p.m,
+                                             T >= 0 ? (T - 1) * s->hop : -1, 20 * s->hop, p.wave, p.cap, st));
+    }
+    s->R = p.R_new;
+    s->A = p.A_new;
+    s->steps = (int)p.S_new;
+    s->audio = (int)p.Au_new;
+    s->fin = p.final;
+    s->dead = false;
+    if (n_out) *n_out = p.m;
+    return WRNN_OK;
+}
+
+// The group of one, through the launch-wide windowed kernel
 int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, double *wave, int cap, int *n_out,
                      void *stream) {
     if (!s || !s->h) return WRNN_EINVAL;
     wrnn_t *h = s->h;
+    hipStream_t st = (hipStream_t)stream;
     if (n_out) *n_out = 0;
-    if (s->dead) return fail(h, WRNN_EINVAL, "the session failed in an earlier push: close it");
-    if (s->fin) return fail(h, WRNN_EINVAL, "push after the final one: the session is finished");
-    if (n < 0 || (n > 0 && !mel) || cap < 0) return fail(h, WRNN_EINVAL, "need n >= 0, mel when n > 0, cap >= 0");
-    return stream_push(s, mel, n, final != 0, wave, cap, n_out, (hipStream_t)stream);
+    StreamPush p;
+    p.mel = mel, p.n = n, p.final = final != 0, p.wave = wave, p.cap = cap;
+    if (int rc = stream_check(s, p)) return rc;
+    if (int rc = stream_prepare(s, p, st)) return rc;
+    if (p.S_new > p.S_old) {
+        HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
+        h->last_path = (int)s->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
+        int rc;
+        if (s->path == P_XCD) rc = stream_launches<XcdArgs>(s, p.S_old, (int)p.S_new, p.final, h->xs, launch_xcd, st);
+        else rc = stream_launches<XcdsArgs>(s, p.S_old, (int)p.S_new, p.final, h->xss, launch_xcds, st);
+        if (rc) return rc;
+    }
+    return stream_finish(s, p, n_out, st);
+}
+
+// One persistent launch per time chunk for every member with steps to run: member i's rows take
+// the XCDs after those of the members before it, each over its own window (the kernels' kGrp
+// instantiation).  The terms budget is shared by all those rows; round j runs chunk j of every
+// member that still has one.
+extern "C++" {
+template <typename GroupArgs, typename Slab>
+static int group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPush *ps, int count, const Slab &slab,
+                          hipError_t (*launch)(const GroupArgs &, hipStream_t), hipStream_t st) {
+    int rows = 0, longest = 0;
+    for (int i = 0; i < count; ++i)
+        if (ps[i].S_new > ps[i].S_old) {
+            rows += ss[i]->U;
+            longest = std::max(longest, (int)ps[i].S_new - ps[i].S_old);
+        }
+    if (rows == 0) return WRNN_OK;
+    const int N = ss[0]->N;
+    const char *mb_env = std::getenv("WRNN_TERMS_MB");
+    const double budget = (mb_env ? std::atof(mb_env) : 8192.0) * (1 << 20) / 4.0;   // floats
+    const int Lc_max = (int)std::max(1.0, std::min((double)longest, budget / ((double)rows * N) - 1.0));
+    for (int i = 0; i < count; ++i)
+        if (ps[i].S_new > ps[i].S_old) {
+            const int steps = std::min(Lc_max, (int)ps[i].S_new - ps[i].S_old);
+            HIP_TRY(h, ensure(ss[i]->d_T, ss[i]->T_cap, (size_t)(steps + 1) * ss[i]->U * N));
+        }
+    HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
+    h->last_path = (int)ss[0]->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
+    for (int off = 0; off < longest; off += Lc_max) {
+        GroupArgs g{};
+        g.a.slab = h->d_xslab;
+        g.a.members = h->d_members;
+        g.a.ctl = h->d_ctl;
+        g.a.timeout_ticks = h->timeout_ticks;
+        g.a.s = slab;
+        g.a.windowed = 1;
+        int k = 0;
+        for (int i = 0; i < count; ++i) {
+            wrnn_stream *s = ss[i];
+            const int t0 = ps[i].S_old + off, t_end = (int)ps[i].S_new;
+            if (t0 >= t_end) continue;   // no step (left) in this push: the member takes no XCD
+            const int Lc = std::min(Lc_max, t_end - t0);
+            const bool last = ps[i].final;
+            // one step ahead (the kernels prefetch the terms of t + 1), unless the utterance ends there
+            const int trows = last ? std::min(Lc + 1, t_end - t0) : Lc + 1;
+            HIP_TRY(h, launch_terms_interp_win(s->FT.buf[s->FT.cur], (int)s->FT.base, s->AT.buf[s->AT.cur], (int)s->AT.base,
+                                               s->d_coef, s->d_T, N, s->U, s->hop, s->nJ, t0, trows, st));
+            for (int u = 0; u < s->U; ++u, ++k) {
+                XcdRow &r = g.row[k];
+                r.terms = s->d_T + (size_t)u * N;
+                r.terms_ld = (long long)s->U * N;
+                r.noise = s->noise ? s->noise + (size_t)u * 11 : nullptr;
+                r.noise_ld = s->U * 11;
+                r.seed = s->seed;
+                r.row = s->row_offset + u;
+                r.out = s->d_y[s->y_cur] + (size_t)u * s->y_ld[s->y_cur];
+                r.out_t0 = s->y_t0;
+                r.state = s->d_state + (size_t)u * kXcdWgs * s->state_w;
+                r.xg = s->d_xg + (size_t)u * kXXcdStride;
+                r.t0 = t0;
+                r.Lc = Lc;
+                // the end is in sight only in the last push; until then the loop horizon lies past every chunk
+                r.L = last ? t_end : INT_MAX;
+                r.nz_hor = s->noise ? s->noise_steps : INT_MAX;
+            }
+        }
+        g.a.nb = k;
+        HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
+        HIP_TRY(h, launch(g, st));
+    }
+    return WRNN_OK;
+}
+}  // extern "C++"
+
+int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const float *const *mel, const int *n,
+                           const int *final, double *const *wave, const int *cap, int *n_out, void *stream) {
+    if (!sessions || count < 1 || !sessions[0] || !sessions[0]->h) return WRNN_EINVAL;
+    wrnn_t *h = sessions[0]->h;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_out)
+        for (int i = 0; i < count; ++i) n_out[i] = 0;
+    if (!n || !final || !cap) return fail(h, WRNN_EINVAL, "need n, final and cap for every member");
+    // every member is checked before anything is queued for any of them
+    int rows = 0;
+    for (int i = 0; i < count; ++i) {
+        if (!sessions[i]) return fail(h, WRNN_EINVAL, "member " + std::to_string(i) + " is null");
+        if (sessions[i]->h != h) return fail(h, WRNN_EINVAL, "member " + std::to_string(i) + " belongs to another handle");
+        for (int j = 0; j < i; ++j)
+            if (sessions[j] == sessions[i])
+                return fail(h, WRNN_EINVAL, "members " + std::to_string(j) + " and " + std::to_string(i) + " are the same session");
+        if (sessions[i]->path != sessions[0]->path)
+            return fail(h, WRNN_EINVAL, "member " + std::to_string(i) + " runs another loop kernel than member 0");
+        rows += sessions[i]->U;
+    }
+    if (rows > kXcds)
+        return fail(h, WRNN_EINVAL, "a group has at most " + std::to_string(kXcds) + " rows (one per XCD): these members have " +
+                                        std::to_string(rows));
+    std::vector<StreamPush> ps(count);
+    for (int i = 0; i < count; ++i) {
+        StreamPush &p = ps[i];
+        p.mel = mel ? mel[i] : nullptr, p.n = n[i], p.final = final[i] != 0;
+        p.wave = wave ? wave[i] : nullptr, p.cap = cap[i];
+        if (int rc = stream_check(sessions[i], p)) {
+            const std::string why = h->err;
+            return fail(h, rc, "member " + std::to_string(i) + ": " + why);
+        }
+    }
+    // queuing begins: a failure from here on leaves the stores of the members already prepared out of
+    // step with their counts, and the launch is shared, so it kills every member
+    for (int i = 0; i < count; ++i) sessions[i]->dead = true;
+    for (int i = 0; i < count; ++i)
+        if (int rc = stream_prepare(sessions[i], ps[i], st)) return rc;
+    int rc;
+    if (sessions[0]->path == P_XCD) rc = group_launches<XcdGroupArgs>(h, sessions, ps.data(), count, h->xs, launch_xcd_group, st);
+    else rc = group_launches<XcdsGroupArgs>(h, sessions, ps.data(), count, h->xss, launch_xcds_group, st);
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i)
+        if (int rc2 = stream_finish(sessions[i], ps[i], n_out ? &n_out[i] : nullptr, st)) return rc2;
+    return WRNN_OK;
 }
 
 int wrnn_check(wrnn_t *h, void *stream) {

@@ -95,6 +95,30 @@ struct XcdArgs {
     int windowed, nz_hor, out_ld, out_t0;
 };
 
+// Grouped launches (streaming sessions advancing independently, wrnn_stream_push_group): XCD k
+// runs row k of a table of these in place of the launch-wide window — every hand-off of a row
+// stays inside its XCD, so its step window, terms, draws, state, granules and output are its own.
+// Pointers are the ROW's (the session's buffers already offset to its utterance).  The kernels'
+// kGrp instantiation alone reads the table; a row with Lc = 0 takes no XCD.
+struct XcdRow {
+    const float *terms;           // the row's terms of step t0; step t at + (t − t0)·terms_ld (+ c·kXTerms)
+    const float *noise;           // the row's draws of step 0; step t at + t·noise_ld, or nullptr (Philox)
+    float *out;                   // the row's samples: step t at out[t − out_t0]
+    float *state;                 // [kXcdWgs][state width of the kernel]
+    unsigned long long *xg;       // [kXXcdStride] granules
+    unsigned long long seed;
+    long long row;                // global row id (Philox key)
+    long long terms_ld;           // floats between consecutive steps: (utterances of the session)·N
+    int noise_ld;                 // floats between consecutive steps of draws: (utterances of the session)·11
+    int out_t0;
+    int t0, Lc, L, nz_hor;        // as XcdArgs' (windowed), per row
+};
+
+struct XcdGroupArgs {
+    XcdArgs a;                    // slab, members, ctl, timeout_ticks, s, nb = rows in the table; the rest unread
+    XcdRow row[kXcds];
+};
+
 struct XcdLds {
     int whh1, whh2, h1, h2, sg, w3, f2x, ring, nz, gh2, cst, xs, misc, total;
 };

@@ -36,6 +36,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "fatchord_loop.h"
 #include "fatchord_xcd.h"
 #include "wrnn_device.h"
@@ -74,21 +76,28 @@ namespace wrnn {
 #endif
 #define XSTAMPW(kk, w)                                                                                        \
     do {                                                                                                      \
-        if (kDbg && a.dbg && wave == (w) && lane == 0 && t - a.t0 < a.dbg_steps &&                            \
+        if (kDbg && a.dbg && wave == (w) && lane == 0 && t - t0 < a.dbg_steps &&                            \
             (!WRNN_XCD_BAR_STAMPS || ((kk) != 3 && ((kk) < 9 || (kk) > 14))))                                 \
-            a.dbg[((size_t)mem * a.dbg_steps + (t - a.t0)) * kStamps + (kk)] = (unsigned)__builtin_amdgcn_s_memrealtime(); \
+            a.dbg[((size_t)mem * a.dbg_steps + (t - t0)) * kStamps + (kk)] = (unsigned)__builtin_amdgcn_s_memrealtime(); \
     } while (0)
 #define XSTAMP(kk) XSTAMPW(kk, 0)
 // diagnostics (WRNN_XCD_BAR_STAMPS): waves 1..6 → stamps 9..14, wave 7 → stamp 3, at the step-end barrier
 #define XSTAMP_BAR()                                                                                          \
     do {                                                                                                      \
-        if (WRNN_XCD_BAR_STAMPS && kDbg && a.dbg && wave > 0 && lane == 0 && t - a.t0 < a.dbg_steps)          \
-            a.dbg[((size_t)mem * a.dbg_steps + (t - a.t0)) * kStamps + (wave == 7 ? 3 : 8 + wave)] =          \
+        if (WRNN_XCD_BAR_STAMPS && kDbg && a.dbg && wave > 0 && lane == 0 && t - t0 < a.dbg_steps)          \
+            a.dbg[((size_t)mem * a.dbg_steps + (t - t0)) * kStamps + (wave == 7 ? 3 : 8 + wave)] =          \
                 (unsigned)__builtin_amdgcn_s_memrealtime();                                                   \
     } while (0)
 
-template <bool kDbg, bool kWin>
-__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
+__device__ __forceinline__ const XcdArgs &launch_args(const XcdArgs &ka) { return ka; }
+__device__ __forceinline__ const XcdArgs &launch_args(const XcdGroupArgs &ka) { return ka.a; }
+
+// kGrp (grouped launches, fatchord_xcd.h: XcdRow): the row's window, operands and results come from
+// row k of the table instead of the launch-wide fields; the steps themselves are the same code
+template <bool kDbg, bool kWin, bool kGrp = false>
+__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditional_t<kGrp, XcdGroupArgs, XcdArgs> ka) {
+    static_assert(!kGrp || (kWin && !kDbg), "grouped launches are windowed and carry no stamps");
+    const XcdArgs &a = launch_args(ka);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int R = 512, TW = kXcdWgs * kXTerms;
     const XcdLds ll = xcd_lds_layout();
@@ -104,8 +113,14 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     if (tid == 0) {
         const int k = (int)xcc_id();
         int c = kXcdWgs;
-        if (k < a.nb) c = atomicAdd(&a.members[k], 1);
-        misc[1] = (k < a.nb && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        if constexpr (kGrp) {   // a row without steps takes no XCD: its workgroups leave here
+            const bool in = k < a.nb && ka.row[k].Lc > 0;
+            if (in) c = atomicAdd(&a.members[k], 1);
+            misc[1] = (in && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        } else {
+            if (k < a.nb) c = atomicAdd(&a.members[k], 1);
+            misc[1] = (k < a.nb && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        }
         misc[0] = 0;
         for (int i = 2; i < 8; ++i) misc[i] = 0;
     }
@@ -115,10 +130,27 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     if (mem < 0) return;
     const int k = mem / kXcdWgs, c = mem - k * kXcdWgs;
     const int b = a.b0 + k;
-    const int t_end = a.t0 + a.Lc;
-    const int t_terms = min(t_end, a.L - 1);
-    const int nz_hor = kWin ? a.nz_hor : a.L;   // the step below which injected draws exist
-    unsigned long long *xg = a.xg + (size_t)k * kXXcdStride;
+    // the row's step window: the launch's, or (kGrp) its own — k is wave-uniform, the table reads scalar
+    int t0, Lc, L;
+    XcdRow rw{};   // kGrp: row k of the table, read once here
+    if constexpr (kGrp) {
+        rw = ka.row[k];
+        t0 = rw.t0;
+        Lc = rw.Lc;
+        L = rw.L;
+    } else {
+        t0 = a.t0;
+        Lc = a.Lc;
+        L = a.L;
+    }
+    const int t_end = t0 + Lc;
+    const int t_terms = min(t_end, L - 1);
+    int nz_hor;   // the step below which injected draws exist
+    if constexpr (kGrp) nz_hor = rw.nz_hor;
+    else nz_hor = kWin ? a.nz_hor : L;
+    unsigned long long *xg;
+    if constexpr (kGrp) xg = rw.xg;
+    else xg = a.xg + (size_t)k * kXXcdStride;
     auto XG = [&](int hop) { return xg + (size_t)hop * kXHopStride; };
     // publishes through one wave-uniform buffer descriptor + a 32-bit granule index (the 64-bit
     // per-lane pointers of each hop stayed live across the loop and were spilled: the F2 publish
@@ -127,9 +159,19 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     auto XGI = [&](int hop) { return hop * (int)kXHopStride; };
     auto RING = [&](int t) { return ring + (t & (kXRing - 1)) * kXTerms; };
     auto NZ = [&](int t) { return nzr + (t & (kXRing - 1)) * kXNoise; };
-    auto TERMS = [&](int t) { return a.terms + ((size_t)(t - a.t0) * a.nb + k) * TW + (size_t)c * kXTerms; };
+    auto TERMS = [&](int t) {
+        if constexpr (kGrp) return rw.terms + (size_t)(t - t0) * (size_t)rw.terms_ld + (size_t)c * kXTerms;
+        else return a.terms + ((size_t)(t - t0) * a.nb + k) * TW + (size_t)c * kXTerms;
+    };
     const float *S = a.slab + (size_t)c * a.s.total;
-    const unsigned long long prow = (unsigned long long)(a.row0 + k);
+    unsigned long long prow, seed;
+    if constexpr (kGrp) {
+        prow = (unsigned long long)rw.row;
+        seed = rw.seed;
+    } else {
+        prow = (unsigned long long)(a.row0 + k);
+        seed = a.seed;
+    }
 
     // ---- register-resident weights: one role-indexed set of 28 float4 (chunks li + 32m of a row)
     //   GRU2 waves (0, 5..7; group g2): W[12j + 4q + m] = W_ih2 gate q of unit 4·g2 + 2j + e (slab
@@ -183,8 +225,13 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     // sampler noise of step t → NZ(t): u1 → log(-log u1) (distribution.py:107), u2 → log u2 − log(1 − u2) (:119)
     auto noise_term = [&](int t) -> float {
         float uu;
-        if (a.noise) uu = a.noise[((size_t)t * a.Bt + b) * 11 + lane];
-        else uu = philox_noise(a.seed, prow, (uint32_t)t, (uint32_t)lane, 1);
+        if constexpr (kGrp) {
+            if (rw.noise) uu = rw.noise[(size_t)t * (size_t)rw.noise_ld + lane];
+            else uu = philox_noise(seed, prow, (uint32_t)t, (uint32_t)lane, 1);
+        } else {
+            if (a.noise) uu = a.noise[((size_t)t * a.Bt + b) * 11 + lane];
+            else uu = philox_noise(seed, prow, (uint32_t)t, (uint32_t)lane, 1);
+        }
         return mol_noise_term(uu, lane);
     };
     // GRU1 term(s) of step t for W_hh1 row rr (u·3 + q), by lane 0 / 32 of an engine:
@@ -281,14 +328,16 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
         for (int i = tid; i < kXH2LdsRows * R / 4; i += kXThreads) dst[i] = src[i];
         for (int i = tid; i < kXFcRows * 32; i += kXThreads) w3s[i] = S[a.s.w3 + i];
         for (int i = tid; i < kXCst; i += kXThreads) cst[i] = S[a.s.cst + i];
-        for (int t = a.t0; t < a.t0 + 3; ++t) {
+        for (int t = t0; t < t0 + 3; ++t) {
             if (t <= t_terms)
                 for (int i = tid; i < kXTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];
             if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);
         }
     }
-    const bool resume = a.t0 > 0;
-    float *st = a.state + ((size_t)k * kXcdWgs + c) * kXStateW;
+    const bool resume = t0 > 0;
+    float *st;
+    if constexpr (kGrp) st = rw.state + (size_t)c * kXStateW;
+    else st = a.state + ((size_t)k * kXcdWgs + c) * kXStateW;
     float h1v = resume ? st[tid] : 0.0f;              // h1 of unit tid (recurrent, this thread)
     float h2own = resume ? st[512 + 2048 + 48 + ui] : 0.0f;   // h2 of this lane's GRU2 unit (GRU2 waves)
     // consume the carried-state loads here (an empty asm use: the wait lands before the loop);
@@ -298,7 +347,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     if (resume) {
         for (int i = tid; i < 4 * R; i += kXThreads) sg[i] = st[512 + i];
         if (tid < 48) gh2s[tid] = st[512 + 2048 + tid];
-        if (tid == 0) xs[(a.t0 + 1) & 1] = st[512 + 2048 + 48 + 16];
+        if (tid == 0) xs[(t0 + 1) & 1] = st[512 + 2048 + 48 + 16];
     } else {
         if (tid < 48) gh2s[tid] = 0.0f;
         if (tid == 0) xs[1] = 0.0f;
@@ -318,15 +367,15 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
     if (*abort_flag) return;
 
     if (WRNN_XCD_PRIO && wave == 0) __builtin_amdgcn_s_setprio(WRNN_XCD_PRIO);
-    float x = xs[(a.t0 + 1) & 1];                    // x_{t-1}, wave-uniform
+    float x = xs[(t0 + 1) & 1];                    // x_{t-1}, wave-uniform
     f4v s4 = lds4(sg + 4 * tid);                     // GRU1 terms of unit tid for step t
-    for (int t = a.t0; t < t_end; ++t) {
+    for (int t = t0; t < t_end; ++t) {
         const uint32_t tag = (uint32_t)t + 1u;
-        const bool more = t + 1 < a.L;
+        const bool more = t + 1 < L;
         const float *tr = RING(t);
         XSTAMP(0);
-        if (kDbg && a.dbg && wave == 0 && lane == 0 && t - a.t0 < a.dbg_steps)   // shader clock beside the 100 MHz one
-            a.dbg[((size_t)mem * a.dbg_steps + (t - a.t0)) * kStamps + 15] = (unsigned)__builtin_amdgcn_s_memtime();
+        if (kDbg && a.dbg && wave == 0 && lane == 0 && t - t0 < a.dbg_steps)   // shader clock beside the 100 MHz one
+            a.dbg[((size_t)mem * a.dbg_steps + (t - t0)) * kStamps + 15] = (unsigned)__builtin_amdgcn_s_memtime();
         // operands of the GRU2 gate math (this lane's unit ui): LDS reads issued before GRU1's
         // transcendental chain (behind its h1 store the compiler could not move them).  Every wave
         // issues them (the fc waves read units 0..3 and drop the values): under a role branch their
@@ -461,7 +510,11 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
             x = mol_sample_pairs(la, lb, ua, ub, u10, jp);
             if (lane == 0) {
                 xs[t & 1] = x;
-                if (c == 0) a.out[kWin ? (size_t)b * a.out_ld + (t - a.out_t0) : (size_t)b * a.L + t] = x;
+                if constexpr (kGrp) {
+                    if (c == 0) rw.out[t - rw.out_t0] = x;
+                } else {
+                    if (c == 0) a.out[kWin ? (size_t)b * a.out_ld + (t - a.out_t0) : (size_t)b * L + t] = x;
+                }
             }
             XSTAMP(8);
         } else if (wave < kXWaveFc2) {
@@ -577,7 +630,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
             if (WRNN_XCD_SKIP_RECUR) {
                 if (wave == 7) {
                     wait_flag(f1got, tag);
-                    if (t + 2 >= a.t0 + 3) {
+                    if (t + 2 >= t0 + 3) {
                         if (t + 2 <= t_terms && lane < kXTerms / 4)
                             reinterpret_cast<f4v *>(RING(t + 2))[lane] = reinterpret_cast<const f4v *>(TERMS(t + 2))[lane];
                         if (t + 2 < nz_hor && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
@@ -611,7 +664,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
                     gather_terms(t + 1);
                 }
                 XSTAMPW(14, 5);
-            } else if (t + 2 >= a.t0 + 3) {
+            } else if (t + 2 >= t0 + 3) {
                 // ring: step t+2's terms and sampler noise, loaded and stored within this window
                 // (a load carried across steps in registers would not fit the VGPR budget, and an
                 // LDS-DMA makes hipcc wait for it before every later LDS access of the issuing wave;
@@ -653,6 +706,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(XcdArgs a) {
 #define WRNN_K_XCD fatchord_xcd_kernel<false, false>
 #define WRNN_K_XCD_DBG fatchord_xcd_kernel<true, false>
 #define WRNN_K_XCD_WIN fatchord_xcd_kernel<false, true>   // streaming sessions (no stamps)
+#define WRNN_K_XCD_GRP fatchord_xcd_kernel<false, true, true>   // group pushes: a window per row
 
 hipError_t launch_xcd(const XcdArgs &a, hipStream_t st) {
     XcdArgs args = a;
@@ -661,8 +715,16 @@ hipError_t launch_xcd(const XcdArgs &a, hipStream_t st) {
     return hipLaunchKernel(kf, dim3(kXcds * kXcdWgs), dim3(kXThreads), params, xcd_lds_layout().total * sizeof(float), st);
 }
 
+hipError_t launch_xcd_group(const XcdGroupArgs &g, hipStream_t st) {
+    XcdGroupArgs args = g;
+    void *params[] = {&args};
+    return hipLaunchKernel((const void *)WRNN_K_XCD_GRP, dim3(kXcds * kXcdWgs), dim3(kXThreads), params,
+                           xcd_lds_layout().total * sizeof(float), st);
+}
+
 hipError_t prepare_xcd_kernel(int max_lds_bytes) {
-    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN}) {
+    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN,
+                           (const void *)WRNN_K_XCD_GRP}) {
         hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
         if (e != hipSuccess) return e;
     }
@@ -671,7 +733,8 @@ hipError_t prepare_xcd_kernel(int max_lds_bytes) {
 
 hipError_t xcd_occupancy(int *blocks_per_cu) {
     int best = 1 << 30;
-    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN}) {
+    for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN,
+                           (const void *)WRNN_K_XCD_GRP}) {
         int n = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kf, kXThreads, xcd_lds_layout().total * sizeof(float));
         if (e != hipSuccess) return e;

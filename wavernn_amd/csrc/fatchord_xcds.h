@@ -70,6 +70,12 @@ struct XcdsArgs {
     int windowed, nz_hor, out_ld, out_t0;
 };
 
+// grouped launches: fatchord_xcd.h's per-row table (terms_ld in units of this kernel's N, state kSStateW wide)
+struct XcdsGroupArgs {
+    XcdsArgs a;                   // slab, members, ctl, timeout_ticks, s, nb = rows in the table; the rest unread
+    XcdRow row[kXcds];
+};
+
 struct XcdsLds {
     int h1, h2, sg, w3, f2x, ring, nz, gh2, cst, xs, misc, whh1b, whh1c, whh2b, whh2c, total;
 };

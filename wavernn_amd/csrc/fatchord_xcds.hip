@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "fatchord_loop.h"
 #include "fatchord_xcds.h"
 #include "wrnn_device.h"
@@ -160,21 +162,28 @@ __device__ __forceinline__ float sp_block_row(const f4v (&wa)[4], const f4v (&wb
 
 #define XSTAMPW(kk, w)                                                                                        \
     do {                                                                                                      \
-        if (kDbg && a.dbg && wave == (w) && lane == 0 && t - a.t0 < a.dbg_steps &&                            \
+        if (kDbg && a.dbg && wave == (w) && lane == 0 && t - t0 < a.dbg_steps &&                            \
             (!WRNN_XCD_BAR_STAMPS || ((kk) != 3 && ((kk) < 9 || (kk) > 14))))                                 \
-            a.dbg[((size_t)mem * a.dbg_steps + (t - a.t0)) * kStamps + (kk)] = (unsigned)__builtin_amdgcn_s_memrealtime(); \
+            a.dbg[((size_t)mem * a.dbg_steps + (t - t0)) * kStamps + (kk)] = (unsigned)__builtin_amdgcn_s_memrealtime(); \
     } while (0)
 #define XSTAMP(kk) XSTAMPW(kk, 0)
 // diagnostics (WRNN_XCD_BAR_STAMPS): waves 1..6 → stamps 9..14, wave 7 → stamp 3, at the step-end barrier
 #define XSTAMP_BAR()                                                                                          \
     do {                                                                                                      \
-        if (WRNN_XCD_BAR_STAMPS && kDbg && a.dbg && wave > 0 && lane == 0 && t - a.t0 < a.dbg_steps)          \
-            a.dbg[((size_t)mem * a.dbg_steps + (t - a.t0)) * kStamps + (wave == 7 ? 3 : 8 + wave)] =          \
+        if (WRNN_XCD_BAR_STAMPS && kDbg && a.dbg && wave > 0 && lane == 0 && t - t0 < a.dbg_steps)          \
+            a.dbg[((size_t)mem * a.dbg_steps + (t - t0)) * kStamps + (wave == 7 ? 3 : 8 + wave)] =          \
                 (unsigned)__builtin_amdgcn_s_memrealtime();                                                   \
     } while (0)
 
-template <bool kDbg, bool kWin>
-__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a) {
+__device__ __forceinline__ const XcdsArgs &launch_args(const XcdsArgs &ka) { return ka; }
+__device__ __forceinline__ const XcdsArgs &launch_args(const XcdsGroupArgs &ka) { return ka.a; }
+
+// kGrp (grouped launches, fatchord_xcd.h: XcdRow): the row's window, operands and results come from
+// row k of the table instead of the launch-wide fields; the steps themselves are the same code
+template <bool kDbg, bool kWin, bool kGrp = false>
+__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::conditional_t<kGrp, XcdsGroupArgs, XcdsArgs> ka) {
+    static_assert(!kGrp || (kWin && !kDbg), "grouped launches are windowed and carry no stamps");
+    const XcdsArgs &a = launch_args(ka);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int R = kSR, TW = kXcdWgs * kSTerms;
     const XcdsLds ll = xcds_lds_layout();
@@ -193,8 +202,14 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     if (tid == 0) {
         const int k = (int)xcc_id();
         int c = kXcdWgs;
-        if (k < a.nb) c = atomicAdd(&a.members[k], 1);
-        misc[1] = (k < a.nb && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        if constexpr (kGrp) {   // a row without steps takes no XCD: its workgroups leave here
+            const bool in = k < a.nb && ka.row[k].Lc > 0;
+            if (in) c = atomicAdd(&a.members[k], 1);
+            misc[1] = (in && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        } else {
+            if (k < a.nb) c = atomicAdd(&a.members[k], 1);
+            misc[1] = (k < a.nb && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        }
         misc[0] = 0;
         for (int i = 2; i < 8; ++i) misc[i] = 0;
     }
@@ -204,18 +219,53 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     if (mem < 0) return;
     const int k = mem / kXcdWgs, c = mem - k * kXcdWgs;
     const int b = a.b0 + k;
-    const int t_end = a.t0 + a.Lc;
-    const int t_terms = min(t_end, a.L - 1);
-    const int nz_hor = kWin ? a.nz_hor : a.L;   // the step below which injected draws exist
-    unsigned long long *xg = a.xg + (size_t)k * kXXcdStride;
+    // the row's step window: the launch's, or (kGrp) its own — k is wave-uniform, the table reads scalar
+    int t0, Lc, L;
+    XcdRow rw{};   // kGrp: row k of the table, read once here
+    if constexpr (kGrp) {
+        rw = ka.row[k];
+        t0 = rw.t0;
+        Lc = rw.Lc;
+        L = rw.L;
+    } else {
+        t0 = a.t0;
+        Lc = a.Lc;
+        L = a.L;
+    }
+    const int t_end = t0 + Lc;
+    const int t_terms = min(t_end, L - 1);
+    int nz_hor;   // the step below which injected draws exist
+    if constexpr (kGrp) nz_hor = rw.nz_hor;
+    else nz_hor = kWin ? a.nz_hor : L;
+    unsigned long long *xg;
+    if constexpr (kGrp) xg = rw.xg;
+    else xg = a.xg + (size_t)k * kXXcdStride;
+    // injected draws of step t (null: Philox)
+    const float *nzp;
+    if constexpr (kGrp) nzp = rw.noise;
+    else nzp = a.noise;
+    auto DRAW = [&](int t, int lane_) {
+        if constexpr (kGrp) return nzp[(size_t)t * (size_t)rw.noise_ld + lane_];
+        else return nzp[((size_t)t * a.Bt + b) * 11 + lane_];
+    };
     auto XG = [&](int hop) { return xg + (size_t)hop * kXHopStride; };
     const __amdgpu_buffer_rsrc_t xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);   // publishes
     auto XGI = [&](int hop) { return hop * (int)kXHopStride; };                                          // granule index
     auto RING = [&](int t) { return ring + (t & (kXRing - 1)) * kSTerms; };
     auto NZ = [&](int t) { return nzr + (t & (kXRing - 1)) * kXNoise; };
-    auto TERMS = [&](int t) { return a.terms + ((size_t)(t - a.t0) * a.nb + k) * TW + (size_t)c * kSTerms; };
+    auto TERMS = [&](int t) {
+        if constexpr (kGrp) return rw.terms + (size_t)(t - t0) * (size_t)rw.terms_ld + (size_t)c * kSTerms;
+        else return a.terms + ((size_t)(t - t0) * a.nb + k) * TW + (size_t)c * kSTerms;
+    };
     const float *S = a.slab + (size_t)c * a.s.total;
-    const unsigned long long prow = (unsigned long long)(a.row0 + k);
+    unsigned long long prow, seed;
+    if constexpr (kGrp) {
+        prow = (unsigned long long)rw.row;
+        seed = rw.seed;
+    } else {
+        prow = (unsigned long long)(a.row0 + k);
+        seed = a.seed;
+    }
 
     // ---- register-resident weights
     //   wg (waves 0..6, engines 0..2): the two W_ih2 blocks of this lane in gate block-row
@@ -272,8 +322,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     // sampler noise of step t → NZ(t): u1 → log(-log u1) (distribution.py:107), u2 → log u2 − log(1 − u2) (:119)
     auto noise_term = [&](int t) -> float {
         float uu;
-        if (a.noise) uu = a.noise[((size_t)t * a.Bt + b) * 11 + lane];
-        else uu = philox_noise(a.seed, prow, (uint32_t)t, (uint32_t)lane, 1);
+        if (nzp) uu = DRAW(t, lane);
+        else uu = philox_noise(seed, prow, (uint32_t)t, (uint32_t)lane, 1);
         return mol_noise_term(uu, lane);
     };
     // GRU1 term(s) of step t for row rr (u·3 + q):
@@ -359,7 +409,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
         }
         for (int i = tid; i < kXFcRows * 32; i += kXThreads) w3s[i] = S[a.s.w3 + i];
         for (int i = tid; i < kSCst; i += kXThreads) cst[i] = S[a.s.cst + i];
-        for (int t = a.t0; t < a.t0 + 3; ++t) {
+        for (int t = t0; t < t0 + 3; ++t) {
             if (t <= t_terms)
                 for (int i = tid; i < kSTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];
             if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);
@@ -369,11 +419,13 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     // conditioning terms (lanes < 57, one float4 each) and the injected sampler noise (lanes < 11)
     auto stage_ring = [&](int t) {
         if (t <= t_terms && lane < kSTerms / 4) wg[0] = reinterpret_cast<const f4v *>(TERMS(t))[lane];
-        if (a.noise && t < nz_hor && lane < 11) wg[1].x = a.noise[((size_t)t * a.Bt + b) * 11 + lane];
+        if (nzp && t < nz_hor && lane < 11) wg[1].x = DRAW(t, lane);
     };
-    if (wave == 7) stage_ring(a.t0 + 3);
-    const bool resume = a.t0 > 0;
-    float *st = a.state + ((size_t)k * kXcdWgs + c) * kSStateW;
+    if (wave == 7) stage_ring(t0 + 3);
+    const bool resume = t0 > 0;
+    float *st;
+    if constexpr (kGrp) st = rw.state + (size_t)c * kSStateW;
+    else st = a.state + ((size_t)k * kXcdWgs + c) * kSStateW;
     constexpr int oSG = kSR, oGH2 = kSR + 4 * kSR, oH2 = oGH2 + 84, oX = oH2 + kSU;
     float h1v = resume ? st[tid] : 0.0f;               // h1 of units tid, tid + 512 (this thread)
     float h1v2 = (resume && two) ? st[u2] : 0.0f;
@@ -381,7 +433,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     if (resume) {
         for (int i = tid; i < 4 * R; i += kXThreads) sg[i] = st[oSG + i];
         if (tid < 84) gh2s[tid] = st[oGH2 + tid];
-        if (tid == 0) xs[(a.t0 + 1) & 1] = st[oX];
+        if (tid == 0) xs[(t0 + 1) & 1] = st[oX];
     } else {
         if (tid < 84) gh2s[tid] = 0.0f;
         if (tid == 0) xs[1] = 0.0f;
@@ -400,11 +452,11 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
     __syncthreads();
     if (*abort_flag) return;
 
-    float x = xs[(a.t0 + 1) & 1];                    // x_{t-1}, wave-uniform
+    float x = xs[(t0 + 1) & 1];                    // x_{t-1}, wave-uniform
     f4v s4 = lds4(sg + 4 * tid), s4b = lds4(sg + 4 * u2);
-    for (int t = a.t0; t < t_end; ++t) {
+    for (int t = t0; t < t_end; ++t) {
         const uint32_t tag = (uint32_t)t + 1u;
-        const bool more = t + 1 < a.L;
+        const bool more = t + 1 < L;
         const float *tr = RING(t);
         XSTAMP(0);
         // operands of the GRU2 gate math (unit ul), read before GRU1
@@ -589,7 +641,11 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
                 x = mol_sample_pairs(la, lb, ua, ub, u10, jp);
                 if (lane == 0) {
                     xs[t & 1] = x;
-                    if (c == 0) a.out[kWin ? (size_t)b * a.out_ld + (t - a.out_t0) : (size_t)b * a.L + t] = x;
+                    if constexpr (kGrp) {
+                        if (c == 0) rw.out[t - rw.out_t0] = x;
+                    } else {
+                        if (c == 0) a.out[kWin ? (size_t)b * a.out_ld + (t - a.out_t0) : (size_t)b * L + t] = x;
+                    }
                 }
                 XSTAMP(8);
             }
@@ -631,7 +687,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
                 if (wave == 7) {
                     if (t + 3 <= t_terms && lane < kSTerms / 4) reinterpret_cast<f4v *>(RING(t + 3))[lane] = wg[0];
                     if (t + 3 < nz_hor && lane < 11)
-                        NZ(t + 3)[lane] = mol_noise_term(a.noise ? wg[1].x : philox_noise(a.seed, prow, (uint32_t)(t + 3), (uint32_t)lane, 1), lane);
+                        NZ(t + 3)[lane] = mol_noise_term(nzp ? wg[1].x : philox_noise(seed, prow, (uint32_t)(t + 3), (uint32_t)lane, 1), lane);
                     stage_ring(t + 4);
                     if (!WRNN_XCDS_GRU2_STAMPS) XSTAMPW(12, 7);
                 }
@@ -664,6 +720,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(XcdsArgs a)
 #define WRNN_K_XCDS fatchord_xcds_kernel<false, false>
 #define WRNN_K_XCDS_DBG fatchord_xcds_kernel<true, false>
 #define WRNN_K_XCDS_WIN fatchord_xcds_kernel<false, true>   // streaming sessions (no stamps)
+#define WRNN_K_XCDS_GRP fatchord_xcds_kernel<false, true, true>   // group pushes: a window per row
 
 hipError_t launch_xcds(const XcdsArgs &a, hipStream_t st) {
     XcdsArgs args = a;
@@ -672,8 +729,16 @@ hipError_t launch_xcds(const XcdsArgs &a, hipStream_t st) {
     return hipLaunchKernel(kf, dim3(kXcds * kXcdWgs), dim3(kXThreads), params, xcds_lds_layout().total * sizeof(float), st);
 }
 
+hipError_t launch_xcds_group(const XcdsGroupArgs &g, hipStream_t st) {
+    XcdsGroupArgs args = g;
+    void *params[] = {&args};
+    return hipLaunchKernel((const void *)WRNN_K_XCDS_GRP, dim3(kXcds * kXcdWgs), dim3(kXThreads), params,
+                           xcds_lds_layout().total * sizeof(float), st);
+}
+
 hipError_t prepare_xcds_kernel(int max_lds_bytes) {
-    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN}) {
+    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN,
+                           (const void *)WRNN_K_XCDS_GRP}) {
         hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
         if (e != hipSuccess) return e;
     }
@@ -682,7 +747,8 @@ hipError_t prepare_xcds_kernel(int max_lds_bytes) {
 
 hipError_t xcds_occupancy(int *blocks_per_cu) {
     int best = 1 << 30;
-    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN}) {
+    for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN,
+                           (const void *)WRNN_K_XCDS_GRP}) {
         int n = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kf, kXThreads, xcds_lds_layout().total * sizeof(float));
         if (e != hipSuccess) return e;

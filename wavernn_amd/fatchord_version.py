@@ -378,6 +378,29 @@ class WaveRNN(nn.Module):
         takes.  Modes and dims the session kernels do not cover raise NotImplementedError."""
         return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset)
 
+    def push_streams(self, pushes) -> list:
+        """Advance several sessions of this model in one call: `pushes` is a sequence of
+        (WaveRNNStream, mel_chunk or None, final) → one float64 numpy array [U_i][m_i] per member,
+        what stream.push(mel_chunk) (or finish(), with final) returns for each, bit for bit.
+        Inside a session the utterances advance in lock step: the same frames in the same push, one
+        total_frames, one end.  A group lifts that between sessions — requests that arrived at
+        different times, with different lengths, whose frames come in at different moments: each
+        member gets its own frames and its own end, and all of them share one persistent launch per
+        push, every row on its own XCD (C-ABI wrnn_stream_push_group), instead of one launch per
+        session that leaves seven XCDs idle.  The members' rows together are at most 8; a finished
+        session is no longer listed.  Refusals raise ValueError and leave every member unchanged."""
+        members = []
+        for item in pushes:
+            if not isinstance(item, (tuple, list)) or len(item) != 3 or not isinstance(item[0], WaveRNNStream):
+                raise ValueError("pushes holds (WaveRNNStream, mel_chunk or None, final) tuples")
+            s, mel, final = item
+            if s._model is not self:
+                raise ValueError("a member session belongs to another model")
+            members.append((s._session, s._mel_tensor(mel), bool(final)))
+        if not members:
+            raise ValueError("push_streams needs at least one member")
+        return [w.cpu().numpy() for w in self.loop_handle().push_streams(members)]
+
     def generate_stream(self, mels, chunk_frames: int = 8, *, noise=None, seed: Optional[int] = None,
                         row_offset: int = 0):
         """generate(mels, None, False, ...) as a generator of float64 chunks, for a mel known up
@@ -499,7 +522,8 @@ class WaveRNN(nn.Module):
 class WaveRNNStream:
     """The session WaveRNN.stream() returns: push(mel_chunk) → float64 [U][m] (m may be 0),
     finish() → the tail; a context manager; `lookahead_frames` is how many frames behind the
-    newest one the loop runs (voc_pad + 1)."""
+    newest one the loop runs (voc_pad + 1).  Its `n_streams` utterances advance in lock step;
+    WaveRNN.push_streams advances several sessions in one call, each at its own pace."""
 
     def __init__(self, model: WaveRNN, n_streams: int, total_frames: Optional[int], noise, seed: Optional[int],
                  row_offset: int):
@@ -508,6 +532,7 @@ class WaveRNNStream:
             raise RuntimeError("WaveRNN.stream runs on the MI355X HIP path: move the model to a GPU "
                                "(model.to('cuda')); there is no CPU fallback")
         self.device = device
+        self._model = model
         nz = None
         if noise is not None:
             nz = torch.as_tensor(noise, dtype=torch.float32).to(device).contiguous()
@@ -519,11 +544,16 @@ class WaveRNNStream:
         self.n_streams = n_streams
         self.lookahead_frames = self._session.lookahead_frames
 
-    def push(self, mel_chunk) -> np.ndarray:
+    def _mel_tensor(self, mel_chunk):
+        if mel_chunk is None:
+            return None
         mel = torch.as_tensor(mel_chunk, device=self.device).to(torch.float32)
         if mel.dim() == 2:
             mel = mel[None]
-        return self._session.push(mel.contiguous()).cpu().numpy()
+        return mel.contiguous()
+
+    def push(self, mel_chunk) -> np.ndarray:
+        return self._session.push(self._mel_tensor(mel_chunk)).cpu().numpy()
 
     def finish(self) -> np.ndarray:
         return self._session.push(None, final=True).cpu().numpy()

@@ -250,6 +250,59 @@ class FatchordLoop:
             self.check(stream)
         return out, labels
 
+    def push_streams(self, pushes, stream=None, check: bool = True) -> list:
+        """Advance several sessions of this loop in one call (C-ABI wrnn_stream_push_group): `pushes`
+        is a sequence of (FatchordStream, mel or None, final), each member with its own frames and
+        its own end — what FatchordStream.push gives for each, bit for bit, but with one persistent
+        launch per time chunk for all of them, every row on its own XCD.  The members' rows together
+        are at most 8.  → the new audio per member, float64 [U_i][m_i] on the GPU.  Refusals
+        (ValueError with the library's message) leave every member unchanged."""
+        members = []
+        for item in pushes:
+            if not isinstance(item, (tuple, list)) or len(item) != 3:
+                raise ValueError("pushes holds (FatchordStream, mel or None, final) tuples")
+            s, mel, final = item
+            if not isinstance(s, FatchordStream):
+                raise ValueError("pushes holds (FatchordStream, mel or None, final) tuples")
+            if s._s is None:
+                raise ValueError("a member session is closed")
+            if s.loop is not self:
+                raise ValueError("a member session belongs to another loop")
+            if s.finished:
+                raise ValueError("push after finish(): a member session has ended")
+            members.append((s, mel, s._frames_of(mel), bool(final)))
+        if not members:
+            raise ValueError("push_streams needs at least one member")
+        waves, plan = [], []
+        for s, mel, n, final in members:
+            try:
+                m = s.plan(s.frames + n, final) - s.plan(s.frames)
+            except nat.WrnnError as e:
+                raise ValueError(str(e)) from None
+            plan.append(m)
+            waves.append(torch.empty(s.n_streams, m, dtype=torch.float64, device=s.device))
+        count = len(members)
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        vps, ints = ctypes.c_void_p * count, ctypes.c_int * count
+        got = ints()
+        rc = nat.lib().wrnn_stream_push_group(
+            vps(*[s._s.value for s, _, _, _ in members]), count,
+            vps(*[mel.data_ptr() if n else None for _, mel, n, _ in members]), ints(*[n for _, _, n, _ in members]),
+            ints(*[int(f) for _, _, _, f in members]), vps(*[w.data_ptr() if m else None for w, m in zip(waves, plan)]),
+            ints(*plan), got, stream)
+        if rc == -1:   # WRNN_EINVAL: nothing was queued, every member is as before
+            raise ValueError((nat.lib().wrnn_last_error(self._h) or b"").decode(errors="replace"))
+        nat.check(self._h, rc)
+        assert list(got) == plan, (list(got), plan)
+        for s, _, n, final in members:
+            s.frames += n
+            s.finished = final
+        if check:
+            self.check(stream)
+        return waves
+
     def check(self, stream=None) -> None:
         """Synchronise and raise if the persistent kernel aborted (timeout)."""
         if stream is None:
@@ -304,7 +357,9 @@ def stream_lookahead(spec) -> int:
 
 class FatchordStream:
     """A streaming session on a FatchordLoop (C-ABI wrnn_stream_*): `n_streams` utterances in lock
-    step, mel frames pushed as they arrive, float64 audio returned as soon as it is final.  The
+    step (the same frames in the same push, one total, one end; FatchordLoop.push_streams advances
+    several sessions at once, each at its own pace), mel frames pushed as they arrive, float64 audio
+    returned as soon as it is final.  The
     recurrent state, frame-term stores and mel tail live on the GPU in the session, so one-shot
     generate() calls and other sessions on the same loop may run between pushes.  Dims or modes
     the session kernels do not cover raise NotImplementedError with the library's message."""
@@ -345,6 +400,15 @@ class FatchordStream:
         """Samples per utterance the session will have emitted in all once `frames` frames are in."""
         return stream_plan(self.spec, frames, final, self.total_frames)[1]
 
+    def _frames_of(self, mel: Optional[torch.Tensor]) -> int:
+        """The frame count of a push's mel (None: 0), after checking its layout."""
+        if mel is None:
+            return 0
+        if not (isinstance(mel, torch.Tensor) and mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous()
+                and mel.dim() == 3) or tuple(mel.shape[:2]) != (self.n_streams, self.loop.feat_dims):
+            raise ValueError(f"mel must be a contiguous fp32 CUDA tensor [{self.n_streams}][{self.loop.feat_dims}][n]")
+        return mel.shape[2]
+
     def push(self, mel: Optional[torch.Tensor], final: bool = False, stream=None, check: bool = True) -> torch.Tensor:
         """mel [U][feat][n] fp32 on the loop's GPU (None: no frames) → the new audio, float64 [U][m]
         on the GPU (m may be 0).  Asynchronous on `stream` when check=False."""
@@ -352,12 +416,7 @@ class FatchordStream:
             raise RuntimeError("the session is closed")
         if self.finished:
             raise RuntimeError("push after finish(): the session has ended")
-        n = 0
-        if mel is not None:
-            if not (mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.dim() == 3) or \
-                    tuple(mel.shape[:2]) != (self.n_streams, self.loop.feat_dims):
-                raise ValueError(f"mel must be a contiguous fp32 CUDA tensor [{self.n_streams}][{self.loop.feat_dims}][n]")
-            n = mel.shape[2]
+        n = self._frames_of(mel)
         try:
             m = self.plan(self.frames + n, final) - self.plan(self.frames)
         except nat.WrnnError as e:
