@@ -109,7 +109,11 @@ int wrnn_create(const wrnn_config *cfg, int device, wrnn_t **out);
 /* Load weights by reference state_dict name (replaces WaveRNN.load → load_state_dict,
  * fatchord_version.py:414-417, for the loop's tensors: I.*, rnn1.*, rnn2.*, fc1-3.*).
  * Copies and packs into the kernel's per-workgroup layout; the caller keeps ownership.
- * Unknown names are ignored (load_state_dict(strict=False)).  Synchronous. */
+ * Unknown names are ignored (load_state_dict(strict=False)).  Synchronous.
+ * May be called again on a live handle, with all tensors or some: every slab is repacked and
+ * every layout decision taken again (block density <= 1/2: the sparse rows layout where its slab
+ * fits beside one row of state, else the dense one, resident or streamed).  Streaming sessions
+ * opened before the call are refused from then on (wrnn_stream_push). */
 int wrnn_set_weights(wrnn_t *h, const wrnn_tensor *tensors, int n);
 
 /* Run the whole sample loop (fatchord_version.py:192-241) for B rows × L steps.
@@ -234,6 +238,13 @@ int wrnn_melresnet_tile_frames(const wrnn_melresnet_cfg *cfg, int U, int T);
 int wrnn_postprocess(const float *y, int rows, int steps, int batched, int overlap, int mu_law,
                      int n_classes, int wave_len, int fade_len, double *wave, void *stream);
 
+/* Content fingerprints of n device tensors of 32-bit elements (same ABI): out[i] (device, 64 bits
+ * each) = sum over j of (bits of element j + 1) * m(j) modulo 2^64, m(j) = splitmix64(j) | 1.
+ * Exact integer arithmetic, so a change of any single element changes out[i].  One launch per 64
+ * tensors, asynchronous on `stream`.  The drop-in modules key their packed-weight caches on it:
+ * an in-place update through `.data` leaves a tensor's pointer and version counter as they were. */
+int wrnn_fingerprint(const void *const *tensors, const int64_t *numel, int n, uint64_t *out, void *stream);
+
 /* The sampler draws wrnn_generate takes when noise == NULL, materialised (round-6 addition, same
  * ABI): out [steps][rows][K] (device fp32) = draw k of launch row j at step step0 + s, keyed
  * (seed, row_offset + j, step0 + s, k) exactly as every loop kernel keys its in-kernel Philox, so
@@ -308,7 +319,10 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
  * leaves wrnn_elapsed_ms at the last wrnn_generate's launch.  Argument errors (WRNN_EINVAL:
  * counts against the rule above, cap, injected draws too short) are found before anything is
  * queued and leave the session unchanged; any failure after that point kills the session
- * (every later push returns WRNN_EINVAL: close it). */
+ * (every later push returns WRNN_EINVAL: close it).
+ * A session binds the weights the handle held at wrnn_stream_open: after any later
+ * wrnn_set_weights on the handle a push (alone or as a group member) returns WRNN_EINVAL with
+ * that cause and the session is dead; other sessions and one-shot calls are unaffected. */
 int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, double *wave, int cap, int *n_out,
                      void *stream);
 

@@ -21,7 +21,7 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_postprocess", "wrnn_cond_last_error", "wrnn_generate_frames", "wrnn_generate_frames_rows",
            "wrnn_frame_weights", "wrnn_melresnet_floats", "wrnn_melresnet", "wrnn_philox_draws",
            "wrnn_melresnet_tile_frames", "wrnn_stream_open", "wrnn_stream_push", "wrnn_stream_plan",
-           "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group")
+           "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -123,6 +123,8 @@ def lib() -> ctypes.CDLL:
     L.wrnn_stream_lookahead.restype = i32
     L.wrnn_stream_close.argtypes = [vp]
     L.wrnn_stream_close.restype = None
+    L.wrnn_fingerprint.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i64), i32, vp, vp]
+    L.wrnn_fingerprint.restype = i32
     L.wrnn_cond_last_error.argtypes = []
     L.wrnn_cond_last_error.restype = ctypes.c_char_p
     _lib = L

@@ -105,6 +105,7 @@ struct wrnn_ctx {
     SlabLayout s{};
     std::map<std::string, std::vector<float>> w;   // loop tensors, host copies
     bool ready = false;
+    unsigned long long loads = 0;                   // wrnn_set_weights calls that took a tensor (sessions bind one)
     float *d_slab = nullptr, *d_IW = nullptr, *d_Ib = nullptr;
     float *d_cI = nullptr;
     size_t cI_cap = 0;                              // floats
@@ -556,6 +557,9 @@ void set_rows_partition(wrnn_ctx &h, int nbmax) {
     h.rs = make_rows_slab(h, nbmax);
     h.rows_gw = false;
     h.rows_ok = rows_tile_for(h, 1) > 0;
+    // a sparse slab sized by one crowded block-row (W_hh pruned alone: nbmax = R / 4) may not fit
+    // beside one row of state where the dense layout, resident or streamed, does: take that one
+    if (!h.rows_ok && nbmax > 0) return set_rows_partition(h, 0);
     // dense weights beyond the grid's LDS: the same kernel with the slab streamed from HBM
     if (!h.rows_ok && nbmax == 0) {
         h.rows_gw = true;
@@ -2239,6 +2243,8 @@ int wrnn_set_weights(wrnn_t *h, const wrnn_tensor *tensors, int n) {
     if (!h || (n > 0 && !tensors)) return WRNN_EINVAL;
     HIP_TRY(h, hipSetDevice(h->device));
     const auto need = required(h->cfg);
+    // whatever follows, the slabs no longer hold the weights an open session started with
+    if (n > 0) ++h->loads;
     for (int i = 0; i < n; ++i) {
         const wrnn_tensor &t = tensors[i];
         if (!t.name || !t.data) return fail(h, WRNN_EINVAL, "null tensor name/data");
@@ -2591,6 +2597,7 @@ struct wrnn_stream {
     // progress: frames received, aux frames formed, loop steps run, samples emitted
     int R = 0, A = 0, steps = 0, audio = 0;
     bool fin = false, dead = false, primed = false;
+    unsigned long long loads = 0;   // the handle's load count at wrnn_stream_open
     // device state of the session
     float *d_coef = nullptr, *d_state = nullptr, *d_tail[2] = {nullptr, nullptr};
     unsigned long long *d_xg = nullptr;
@@ -2712,6 +2719,7 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
     std::unique_ptr<wrnn_stream, void (*)(wrnn_stream *)> s(new wrnn_stream, wrnn_stream_close);
     s->h = h;
     s->device = h->device;
+    s->loads = h->loads;
     s->path = path;
     s->U = U;
     s->T_known = total_frames;
@@ -2824,6 +2832,13 @@ struct StreamPush {
 
 static int stream_check(wrnn_stream *s, StreamPush &p) {
     wrnn_t *h = s->h;
+    // the slabs a push launches with are the handle's: after a reload they hold another model (or
+    // another kernel's layout), and the session's state belongs to the one it was opened with
+    if (s->loads != h->loads) {
+        s->dead = true;
+        return fail(h, WRNN_EINVAL, "the handle's weights were loaded again (wrnn_set_weights) after this session was "
+                                    "opened: a session binds the weights it was opened with; close it and open a new one");
+    }
     if (s->dead) return fail(h, WRNN_EINVAL, "the session failed in an earlier push: close it");
     if (s->fin) return fail(h, WRNN_EINVAL, "push after the final one: the session is finished");
     if (p.n < 0 || (p.n > 0 && !p.mel) || p.cap < 0) return fail(h, WRNN_EINVAL, "need n >= 0, mel when n > 0, cap >= 0");

@@ -250,6 +250,44 @@ hipError_t launch_postprocess_stream(const float *y, int U, int y_ld, int y_t0, 
     return hipGetLastError();
 }
 
+// ---- content fingerprints (wrnn_fingerprint): one 64-bit sum per tensor, block (chunk, tensor)
+constexpr int kFpMax = 64;        // tensors per launch (the pointer table travels as kernel arguments)
+constexpr int kFpChunks = 32;     // workgroups per tensor
+constexpr int kFpThreads = 256;
+
+struct FpArgs {
+    const uint32_t *p[kFpMax];
+    long long n[kFpMax];
+    unsigned long long *out;      // [count], zeroed before the launch
+};
+
+// splitmix64 of the element index, forced odd: an odd multiplier times a nonzero 32-bit difference
+// is nonzero modulo 2^64, so a change of one element always changes the sum
+__device__ __forceinline__ unsigned long long fp_mix(unsigned long long i) {
+    unsigned long long z = i + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return (z ^ (z >> 31)) | 1ull;
+}
+
+__global__ __launch_bounds__(kFpThreads) void fingerprint_kernel(FpArgs a) {
+    __shared__ unsigned long long sh[kFpThreads];
+    const int t = blockIdx.y;
+    const uint32_t *p = a.p[t];
+    const long long n = a.n[t];
+    unsigned long long h = 0;
+    for (long long i = (long long)blockIdx.x * kFpThreads + threadIdx.x; i < n; i += (long long)kFpChunks * kFpThreads)
+        h += ((unsigned long long)p[i] + 1ull) * fp_mix((unsigned long long)i);
+    sh[threadIdx.x] = h;
+    __syncthreads();
+    for (int s = kFpThreads / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    // integer addition modulo 2^64: the order of the workgroups does not matter
+    if (threadIdx.x == 0 && sh[0] != 0) atomicAdd(&a.out[t], sh[0]);
+}
+
 // error of the last failed stateless call on this thread (also capi.cpp's wrnn_philox_draws)
 thread_local std::string g_cond_err;
 int cond_fail(int code, const std::string &m) {
@@ -408,6 +446,30 @@ int wrnn_postprocess(const float *y, int rows, int steps, int batched, int overl
     hipLaunchKernelGGL(postprocess_kernel, dim3((wave_len + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? WRNN_OK : cond_fail(WRNN_EHIP, hipGetErrorString(e));
+}
+
+int wrnn_fingerprint(const void *const *tensors, const int64_t *numel, int n, uint64_t *out, void *stream) {
+    using namespace wrnn;
+    if (n < 0 || (n > 0 && (!tensors || !numel || !out))) return cond_fail(WRNN_EINVAL, "bad arguments");
+    if (n == 0) return WRNN_OK;
+    for (int i = 0; i < n; ++i)
+        if (numel[i] < 0 || (numel[i] > 0 && !tensors[i])) return cond_fail(WRNN_EINVAL, "null tensor or negative size");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)n * sizeof(uint64_t), st);
+    if (e != hipSuccess) return cond_fail(WRNN_EHIP, hipGetErrorString(e));
+    for (int i0 = 0; i0 < n; i0 += kFpMax) {
+        const int count = n - i0 < kFpMax ? n - i0 : kFpMax;
+        FpArgs a{};
+        for (int i = 0; i < count; ++i) {
+            a.p[i] = static_cast<const uint32_t *>(tensors[i0 + i]);
+            a.n[i] = numel[i0 + i];
+        }
+        a.out = reinterpret_cast<unsigned long long *>(out) + i0;
+        hipLaunchKernelGGL(fingerprint_kernel, dim3(kFpChunks, count), dim3(kFpThreads), 0, st, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return cond_fail(WRNN_EHIP, hipGetErrorString(e));
+    }
+    return WRNN_OK;
 }
 
 }  // extern "C"

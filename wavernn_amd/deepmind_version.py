@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .loop import DM_KEYS, DeepmindLoop
+from .loop import DM_KEYS, DeepmindLoop, content_key
 
 
 class WaveRNN(nn.Module):
@@ -68,13 +68,14 @@ class WaveRNN(nn.Module):
         return {k: sd[k] for k in DM_KEYS}
 
     def loop_handle(self, grid: int = 0) -> DeepmindLoop:
-        """The device handle, (re)packed whenever the weights changed (load, training)."""
+        """The device handle, (re)packed whenever the weights changed: a load, a training step, or
+        an in-place update through `.data`, which only loop.content_key's fingerprint sees."""
         device = next(self.parameters()).device
         if device.type != 'cuda':
             raise RuntimeError("WaveRNN.generate runs on the MI355X HIP path: move the model to a GPU "
                                "(model.to('cuda')); there is no CPU fallback")
         params = self._loop_params()
-        key = (device.index or 0, grid) + tuple((p.data_ptr(), p._version) for p in params.values())
+        key = (device.index or 0, grid) + content_key(params.values(), self.__dict__.setdefault("_fp_loop", {}))
         if self._loop is None or self._loop_key is None or self._loop_key[:2] != key[:2]:
             if self._loop is not None:
                 self._loop.close()

@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from . import condition, dsp
-from .loop import LOOP_KEYS, FatchordLoop, FatchordStream, noise_width
+from .loop import LOOP_KEYS, FatchordLoop, FatchordStream, content_key, noise_width
 
 
 # --------------------------------------------------------------------- upsample network
@@ -165,13 +165,15 @@ class WaveRNN(nn.Module):
         return {k: sd[k] for k in LOOP_KEYS}
 
     def loop_handle(self, grid: int = 0) -> FatchordLoop:
-        """The device handle, (re)packed whenever the loop weights changed (load, training)."""
+        """The device handle, (re)packed whenever the loop weights changed: a load, a training step,
+        or an in-place update through `.data` (the reference pruner's `W *= M`), which only the
+        content fingerprint of loop.content_key sees."""
         device = next(self.parameters()).device
         if device.type != 'cuda':
             raise RuntimeError("WaveRNN.generate runs on the MI355X HIP path: move the model to a GPU "
                                "(model.to('cuda')); there is no CPU fallback")
         params = self._loop_params()
-        key = (device.index or 0, grid) + tuple((p.data_ptr(), p._version) for p in params.values())
+        key = (device.index or 0, grid) + content_key(params.values(), self.__dict__.setdefault("_fp_loop", {}))
         if self._loop is None or self._loop_key is None or self._loop_key[:2] != key[:2]:
             if self._loop is not None:
                 self._loop.close()
@@ -187,7 +189,7 @@ class WaveRNN(nn.Module):
     def _upsample_spec(self) -> condition.UpsampleSpec:
         """Host copy of the box-conv taps, refreshed when those parameters change."""
         convs = [m.weight for m in self.upsample.up_layers if isinstance(m, nn.Conv2d)]
-        key = tuple((w.data_ptr(), w._version) for w in convs)
+        key = content_key(convs, self.__dict__.setdefault("_fp_up", {}))
         if getattr(self, "_up_key", None) != key:
             self._up_spec = condition.UpsampleSpec.from_module(self.upsample, self.feat_dims, self.pad)
             self._up_key = key
@@ -231,8 +233,7 @@ class WaveRNN(nn.Module):
         """(wrnn_melresnet_cfg, packed weights) of the MelResNet, repacked when its parameters or
         BatchNorm statistics changed."""
         res = self.upsample.resnet
-        key = tuple((p.data_ptr(), p._version) for p in res.parameters()) + \
-            tuple((b.data_ptr(), b._version) for b in res.buffers())
+        key = content_key(list(res.parameters()) + list(res.buffers()), self.__dict__.setdefault("_fp_mr", {}))
         if getattr(self, "_mr_key", None) != key:
             self._mr_cfg = condition.melresnet_cfg(res)
             self._mr_packed = condition.melresnet_pack(res)
@@ -375,7 +376,14 @@ class WaveRNN(nn.Module):
         step.  `total_frames`, when known, lets the session emit up to the fade-out instead of
         holding back 21 frames.  `noise` [steps][n_streams][11] injects the sampler draws by
         absolute step; otherwise Philox keyed by `seed` and row_offset + u, the draws generate()
-        takes.  Modes and dims the session kernels do not cover raise NotImplementedError."""
+        takes.  Modes and dims the session kernels do not cover raise NotImplementedError.
+
+        A session binds the weights it was opened with.  Opening it looks at the model's weights
+        (as generate() does); a push does not.  If the loop weights are loaded again while it is
+        open (by a generate() or a new stream() after load_state_dict, a training step or a `.data`
+        update) its next push raises and the session is dead: close it and open a new one.  A
+        change that only pushes would see (a `.data` update with no generate() or stream() after
+        it) is not detected: the session goes on with the weights it was opened with."""
         return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset)
 
     def push_streams(self, pushes) -> list:
@@ -399,7 +407,8 @@ class WaveRNN(nn.Module):
             members.append((s._session, s._mel_tensor(mel), bool(final)))
         if not members:
             raise ValueError("push_streams needs at least one member")
-        return [w.cpu().numpy() for w in self.loop_handle().push_streams(members)]
+        # the members' own loop, as it is: a push does not look at the weights (WaveRNN.stream)
+        return [w.cpu().numpy() for w in members[0][0].loop.push_streams(members)]
 
     def generate_stream(self, mels, chunk_frames: int = 8, *, noise=None, seed: Optional[int] = None,
                         row_offset: int = 0):

@@ -25,6 +25,67 @@ DM_KEYS = ("R.weight", "O1.weight", "O1.bias", "O2.weight", "O2.bias", "O3.weigh
            "O4.bias", "I_coarse.weight", "I_fine.weight", "bias_u", "bias_r", "bias_e")
 
 
+def fingerprint_host(a: np.ndarray) -> int:
+    """wrnn_fingerprint of one tensor, restated in numpy (uint64 arithmetic wraps): the sum over j of
+    (bits of element j + 1) · (splitmix64(j) | 1) modulo 2^64, as a signed 64-bit integer."""
+    bits = np.ascontiguousarray(a, dtype=np.float32).reshape(-1).view(np.uint32).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        z = np.arange(bits.size, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = (z ^ (z >> np.uint64(31))) | np.uint64(1)
+        h = np.add.reduce((bits + np.uint64(1)) * z, dtype=np.uint64)
+    return int(np.array(h, dtype=np.uint64).astype(np.int64))
+
+
+def _fingerprint_args(ts):
+    """What a wrnn_fingerprint call over the floating-point tensors of `ts` needs: None (no such
+    tensor), ("host", arrays) for CPU tensors, or (n, device, pointers, sizes, out, keep, direct) —
+    `direct`: every tensor is read in place (fp32, contiguous), no converted copy was made."""
+    fl = [t.detach() for t in ts if t.is_floating_point() and t.numel()]
+    if not fl:
+        return None
+    if not fl[0].is_cuda:
+        return ("host", fl)
+    keep = [t if t.dtype is torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous() for t in fl]
+    n, dev = len(keep), keep[0].device
+    return (n, dev, (ctypes.c_void_p * n)(*[t.data_ptr() for t in keep]),
+            (ctypes.c_int64 * n)(*[t.numel() for t in keep]), torch.empty(n, dtype=torch.int64, device=dev), keep,
+            all(k is t for k, t in zip(keep, fl)))
+
+
+def content_key(tensors, plan: Optional[dict] = None) -> tuple:
+    """Cache key of a set of tensors: (data_ptr, _version) of each, plus a fingerprint of what each
+    floating-point one holds.  An in-place operation through `.data` (`p.data.mul_(mask)`, the
+    reference pruner's idiom; `conv.weight.data.fill_`) changes neither the pointer nor the version
+    counter, so those alone miss it.  The fingerprints come from the device (C-ABI wrnn_fingerprint:
+    one launch over all tensors, one small readback); exact integer arithmetic on the fp32 bit
+    patterns, so a change of any single element always shows.  CPU tensors: fingerprint_host.
+    `plan`: a dict the caller keeps between calls; it holds the call's argument arrays while the
+    same tensor objects sit at the same addresses (then their dtype and size are the same too)."""
+    ts = list(tensors)
+    ident = tuple((t.data_ptr(), t._version) for t in ts)
+    ptr = tuple(p for p, _ in ident)
+    if plan is not None and plan.get("ptr") == ptr and len(plan["ts"]) == len(ts) and \
+            all(a is b for a, b in zip(plan["ts"], ts)):
+        args = plan["args"]
+    else:
+        args = _fingerprint_args(ts)
+        if plan is not None:
+            plan.clear()
+            if args is not None and args[0] != "host" and args[-1]:
+                plan.update(ts=ts, ptr=ptr, args=args)
+    if args is None:
+        return ident
+    if args[0] == "host":
+        return ident + tuple(fingerprint_host(t.numpy()) for t in args[1])
+    n, dev, ptrs, numel, out = args[:5]
+    with torch.cuda.device(dev):
+        nat.check_cond(nat.lib().wrnn_fingerprint(ptrs, numel, n, out.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream))
+        return ident + tuple(out.tolist())
+
+
 def _round4(n: int) -> int:
     return (n + 3) // 4 * 4
 
