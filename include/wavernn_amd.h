@@ -375,6 +375,63 @@ int wrnn_stream_lookahead(const wrnn_upsample_cfg *ucfg);
 
 void wrnn_stream_close(wrnn_stream_t *s);
 
+/* ---- Lists: U whole utterances of unequal length in one call (list addition, same ABI) -----
+ * A TTS batch: U mels are all there, each a different length, U waveforms go out.  The eight XCDs
+ * are eight LANES; each lane runs a queue of utterances back to back without leaving the
+ * persistent kernel, so no utterance waits for the longest of a batch and no lane idles while
+ * another still has work queued.
+ *
+ * Schedule (wrnn_list_plan; host only, stateless, deterministic): longest-processing-time-first.
+ * The utterances are taken by decreasing frame count (ties: the lower index first) and each goes to
+ * the lane with the smallest load so far (ties: the lowest lane); a lane runs its utterances in
+ * the order they were assigned.
+ *   frames      [U]      frame counts T_i
+ *   lane_of     [U]      out: the lane of utterance i
+ *   pos_in_lane [U]      out: its place in that lane's queue (0 = first)
+ *   lane_frames [lanes]  out: the lane's timeline in frames (the loop runs hop steps per frame:
+ *                        × hop for steps; the schedule is the same in either unit)
+ * WRNN_EINVAL (message in wrnn_cond_last_error) for U < 1, lanes outside 1..8 or any T_i < 21, the
+ * rule wrnn_postprocess enforces.
+ *
+ * Rounds.  A lane's timeline is the concatenation of its utterances' steps.  Launch round j covers
+ * lane-time [j·C, (j+1)·C) on every lane, C = floor(WRNN_TERMS_MB budget / (lanes · N) − 1) steps
+ * (N = terms per row and step; at most the longest timeline) — the rounds are cut by the terms
+ * budget only, never by utterance boundaries.  Inside a round a lane's window is cut into pieces
+ * at utterance boundaries (the tail of A, all of B, the head of C); every piece has its own terms
+ * rows, the one look-ahead row included while its utterance goes on, so a round's terms exceed
+ * lanes · C rows by one row per piece.  One persistent launch per round; a lane whose timeline has
+ * ended takes no XCD in later rounds.  The piece table of all rounds is uploaded once per call:
+ * the host does not wait on the stream between rounds.
+ *
+ * Contract.  out[i] is, bit for bit, what wrnn_generate_frames(h, ucfg, mel[i], aux[i], 1, T[i], 0, 0,
+ * noise[i], seed, row_offset + i, out[i], NULL, stream) writes — for every `lanes` and every
+ * WRNN_TERMS_MB.  Utterance i is Philox row row_offset + i and its step counter starts at 0; each
+ * utterance's frame records and W·frames GEMMs run with exactly the shapes of that single call
+ * (never one GEMM over all utterances: rocBLAS picks its tiling by shape), the per-round
+ * interpolation sums in the single call's order, and the list instantiation of the kernel runs the
+ * same step code.
+ *   mel   [U]  utterance i's [feat_dims][T_i] (device)
+ *   aux   [U]  its MelResNet output [res_out_dims][T_i] (device), as wrnn_generate_frames takes it:
+ *              the caller runs wrnn_melresnet per utterance, with the shapes of a single call
+ *   T     [U]  frame counts, each >= 21
+ *   lanes      1..8
+ *   noise [U]  utterance i's injected draws [hop·T_i][11] by its own step (device), or noise = NULL
+ *              for in-kernel Philox
+ *   out   [U]  utterance i's [hop·T_i] fp32 loop output (device)
+ * Every argument of every utterance is checked before anything is queued (WRNN_EINVAL: the handle
+ * is as before).  WRNN_EUNSUPPORTED under the conditions of wrnn_stream_open: a handle that is
+ * not MoL, rows that run on neither the dense one-row XCD kernel (last_path 5) nor the
+ * block-sparse rnn-896 one (6), or a cascade wrnn_frame_weights refuses.  Queues its work on
+ * `stream` and does not wait for it, except where a workspace must grow (all of them before anything is queued) or the frame weights changed.  One stream per
+ * handle, as wrnn_stream_open states; sessions and one-shot calls on the same handle may run
+ * before and after it in stream order (the call owns its state records and hand-off tags).  Sets
+ * wrnn_info.last_path (5 or 6) and the timing events as wrnn_generate does; kernel aborts surface through
+ * wrnn_check. */
+int wrnn_list_plan(const int *frames, int U, int lanes, int *lane_of, int *pos_in_lane, int64_t *lane_frames);
+int wrnn_generate_list(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *mel, const float *const *aux,
+                       const int *T, int U, int lanes, const float *const *noise, uint64_t seed, int64_t row_offset,
+                       float *const *out, void *stream);
+
 /* Message of the last failed stateless call on this thread. */
 const char *wrnn_cond_last_error(void);
 

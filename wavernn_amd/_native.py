@@ -21,7 +21,8 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_postprocess", "wrnn_cond_last_error", "wrnn_generate_frames", "wrnn_generate_frames_rows",
            "wrnn_frame_weights", "wrnn_melresnet_floats", "wrnn_melresnet", "wrnn_philox_draws",
            "wrnn_melresnet_tile_frames", "wrnn_stream_open", "wrnn_stream_push", "wrnn_stream_plan",
-           "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint")
+           "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint",
+           "wrnn_list_plan", "wrnn_generate_list")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -123,6 +124,13 @@ def lib() -> ctypes.CDLL:
     L.wrnn_stream_lookahead.restype = i32
     L.wrnn_stream_close.argtypes = [vp]
     L.wrnn_stream_close.restype = None
+    # frames [U], U, lanes → lane_of [U], pos_in_lane [U], lane_steps [lanes]
+    L.wrnn_list_plan.argtypes = [pi, i32, i32, pi, pi, ctypes.POINTER(i64)]
+    L.wrnn_list_plan.restype = i32
+    # arrays of U entries: mel, aux pointers, T, (U, lanes), noise pointers (or NULL), seed, row_offset, out pointers
+    L.wrnn_generate_list.argtypes = [vp, ctypes.POINTER(UpsampleCfg), ctypes.POINTER(vp), ctypes.POINTER(vp), pi, i32, i32,
+                                     ctypes.POINTER(vp), u64, i64, ctypes.POINTER(vp), vp]
+    L.wrnn_generate_list.restype = i32
     L.wrnn_fingerprint.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i64), i32, vp, vp]
     L.wrnn_fingerprint.restype = i32
     L.wrnn_cond_last_error.argtypes = []

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <memory>
 #include <cstdlib>
 #include <cstdio>
@@ -54,10 +55,15 @@ hipError_t split_occupancy(int *blocks_per_cu, size_t lds_bytes);
 bool split_has_kernel(int R, int F);
 hipError_t launch_xcd(const XcdArgs &a, hipStream_t st);
 hipError_t launch_xcd_group(const XcdGroupArgs &g, hipStream_t st);
+hipError_t launch_xcd_list(const XcdListArgs &g, hipStream_t st);
+hipError_t launch_terms_interp_list(const XcdPiece *pieces, int p0, int p1, int blocks, const float *coef, int N, int hop,
+                                    int nJ, hipStream_t st);
+int interp_list_blocks(int nt);
 hipError_t prepare_xcd_kernel(int max_lds_bytes);
 hipError_t xcd_occupancy(int *blocks_per_cu);
 hipError_t launch_xcds(const XcdsArgs &a, hipStream_t st);
 hipError_t launch_xcds_group(const XcdsGroupArgs &g, hipStream_t st);
+hipError_t launch_xcds_list(const XcdsListArgs &g, hipStream_t st);
 hipError_t prepare_xcds_kernel(int max_lds_bytes);
 hipError_t xcds_occupancy(int *blocks_per_cu);
 hipError_t launch_xcdm(const XcdmArgs &a, int nq, bool raw, hipStream_t st);
@@ -185,6 +191,16 @@ struct wrnn_ctx {
     float *d_coef = nullptr, *d_FT = nullptr, *d_AT = nullptr, *d_frec = nullptr, *d_cond = nullptr;
     size_t coef_cap = 0, FT_cap = 0, AT_cap = 0, frec_cap = 0, cond_cap = 0;
     std::vector<float> coef_host;                   // the table d_coef holds (re-uploaded when it changes)
+    // list calls (wrnn_generate_list): per-utterance frame-term stores (one arena), recurrent-state
+    // records and granule regions, the device piece table and its pinned staging copy; ev_ltab
+    // marks the end of the last call's table upload (the staging copy is rewritten only after it)
+    float *d_larena = nullptr, *d_lstate = nullptr;
+    size_t larena_cap = 0, lstate_cap = 0;
+    unsigned long long *d_lxg = nullptr;
+    size_t lxg_cap = 0;
+    XcdPiece *d_ltab = nullptr, *h_ltab = nullptr;
+    size_t ltab_cap = 0, hltab_cap = 0;             // records
+    hipEvent_t ev_ltab = nullptr;
 };
 
 namespace {
@@ -1751,20 +1767,28 @@ bool frame_weights(const wrnn_upsample_cfg &c, int *hop_out, int *nJ_out, int *j
 // FT [NF + nJ − 1][U][N] = W·[mel frame | 0 | 0] and AT [NF + 1][U][N] = W·[0 | aux frame | 1]
 // (row NF: W·[0 | 0 | 1]) through the path's own terms GEMM(s): gemm(X, m, C) writes
 // C[m][N] = W·X for X [m][KX] as pack_cond_input lays it out (`split`).
+// FT_dst / AT_dst: stores of the caller's in place of the handle's d_FT / d_AT (wrnn_generate_list:
+// one pair per utterance in its arena); the launches and their shapes are the same.
 template <typename Gemm>
-int frame_terms(wrnn_t *h, const FrameSrc &fs, int N, int KX, int split, hipStream_t st, Gemm gemm) {
+int frame_terms(wrnn_t *h, const FrameSrc &fs, int N, int KX, int split, hipStream_t st, Gemm gemm,
+                float *FT_dst = nullptr, float *AT_dst = nullptr) {
     const int feat = h->cfg.feat_dims, A4 = h->CD - feat;
     const int NFF = fs.NF + fs.nJ - 1, NFA = fs.NF + 1, fmax = std::max(NFF, NFA);
     if (grow(h, h->d_frec, h->frec_cap, (size_t)fmax * fs.U * h->CD) ||
-        grow(h, h->d_X, h->X_cap, (size_t)fmax * fs.U * KX) || grow(h, h->d_FT, h->FT_cap, (size_t)NFF * fs.U * N) ||
-        grow(h, h->d_AT, h->AT_cap, (size_t)NFA * fs.U * N))
+        grow(h, h->d_X, h->X_cap, (size_t)fmax * fs.U * KX))
         return WRNN_EHIP;
+    if (!FT_dst) {
+        if (grow(h, h->d_FT, h->FT_cap, (size_t)NFF * fs.U * N) || grow(h, h->d_AT, h->AT_cap, (size_t)NFA * fs.U * N))
+            return WRNN_EHIP;
+        FT_dst = h->d_FT;
+        AT_dst = h->d_AT;
+    }
     for (int kind = 0; kind < 2; ++kind) {
         const int frames = kind ? NFA : NFF;
         HIP_TRY(h, launch_frame_cond(fs.mel, fs.aux, fs.U, feat, A4, fs.NF, frames, fs.jlo, kind, h->d_frec, st));
         HIP_TRY(h, launch_pack_cond_input(h->d_frec, h->CD, fs.U, 0, fs.U, 0, frames, KX, h->d_X, st, split,
                                           kind ? 1.0f : 0.0f));
-        if (int rc = gemm(h->d_X, frames * fs.U, kind ? h->d_AT : h->d_FT)) return rc;
+        if (int rc = gemm(h->d_X, frames * fs.U, kind ? AT_dst : FT_dst)) return rc;
     }
     return WRNN_OK;
 }
@@ -2552,6 +2576,248 @@ int wrnn_generate_frames_rows(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const fl
     return run_loop(h, path, nullptr, &fs, B, L, noise, seed, row_offset, out, labels, st);
 }
 
+// ---- lists (wavernn_amd.h: wrnn_list_plan, wrnn_generate_list) ------------------------------
+// Longest-processing-time-first over `lanes` lanes: utterances by decreasing length (ties: lower
+// index first), each to the lane with the smallest load so far (ties: lowest lane); a lane runs
+// its utterances in the order they were assigned.
+static void list_plan(const int *frames, int U, int lanes, int *lane_of, int *pos_in_lane, int64_t *lane_len,
+                      std::vector<int> *queue = nullptr) {   // queue [lanes]: the lanes' utterances in running order
+    std::vector<int> order(U);
+    for (int i = 0; i < U; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return frames[x] > frames[y]; });
+    std::vector<int> count(lanes, 0);
+    for (int k = 0; k < lanes; ++k) lane_len[k] = 0;
+    for (int i : order) {
+        int best = 0;
+        for (int k = 1; k < lanes; ++k)
+            if (lane_len[k] < lane_len[best]) best = k;
+        lane_of[i] = best;
+        pos_in_lane[i] = count[best]++;
+        lane_len[best] += frames[i];
+        if (queue) queue[best].push_back(i);
+    }
+}
+
+int wrnn_list_plan(const int *frames, int U, int lanes, int *lane_of, int *pos_in_lane, int64_t *lane_frames) {
+    if (!frames || !lane_of || !pos_in_lane || !lane_frames) return cond_fail(WRNN_EINVAL, "need frames, lane_of, pos_in_lane and lane_frames");
+    if (U < 1) return cond_fail(WRNN_EINVAL, "a list has at least one utterance");
+    if (lanes < 1 || lanes > kXcds) return cond_fail(WRNN_EINVAL, "lanes is 1.." + std::to_string(kXcds));
+    for (int i = 0; i < U; ++i)
+        if (frames[i] < 21)
+            return cond_fail(WRNN_EINVAL, "utterance " + std::to_string(i) + " has " + std::to_string(frames[i]) +
+                                              " frames: fewer than 21 (the fade-out, as wrnn_postprocess)");
+    list_plan(frames, U, lanes, lane_of, pos_in_lane, lane_frames);
+    return WRNN_OK;
+}
+
+int wrnn_generate_list(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *mel, const float *const *aux,
+                       const int *T, int U, int lanes, const float *const *noise, uint64_t seed, int64_t row_offset,
+                       float *const *out, void *stream) {
+    if (!h) return WRNN_EINVAL;
+    if (!h->ready) return fail(h, WRNN_ENOWEIGHTS, "weights not (fully) set");
+    // ---- every argument of every utterance, before anything is queued or any workspace touched
+    if (!ucfg || !mel || !T || !out || U < 1) return fail(h, WRNN_EINVAL, "need ucfg, mel, T, out and U >= 1");
+    if (lanes < 1 || lanes > kXcds) return fail(h, WRNN_EINVAL, "lanes is 1.." + std::to_string(kXcds) + " (one per XCD)");
+    if (h->dm || h->cfg.mode != WRNN_MODE_MOL)
+        return fail(h, WRNN_EUNSUPPORTED, "lists run the one-row XCD MoL kernels: this handle is not MoL");
+    const LoopPath path = choose_path(h, lanes);
+    if (path != P_XCD && path != P_XCDS)
+        return fail(h, WRNN_EUNSUPPORTED,
+                    "lists run the dense rnn/fc 512 XCD kernel or the block-sparse rnn 896 one; " + std::to_string(lanes) +
+                        " row(s) of this handle take loop path " + std::to_string((int)path));
+    const int feat = h->cfg.feat_dims, A4 = h->CD - feat;
+    if (ucfg->feat_dims != feat || ucfg->res_out_dims != A4)
+        return fail(h, WRNN_EINVAL, "upsample config does not match the handle's feat / aux dims");
+    if (ucfg->n_scales < 1 || ucfg->n_scales > 4) return fail(h, WRNN_EINVAL, "1..4 upsample scales");
+    for (int i = 0; i < ucfg->n_scales; ++i)
+        if (ucfg->scales[i] < 1 || !ucfg->taps[i]) return fail(h, WRNN_EINVAL, "bad upsample scale / taps");
+    if (A4 > 0 && !aux) return fail(h, WRNN_EINVAL, "need aux (MelResNet outputs)");
+    int hop = 1, nJ = 1, jlo = 0;
+    std::vector<float> coef;
+    if (!frame_weights(*ucfg, &hop, &nJ, &jlo, coef))
+        return fail(h, WRNN_EUNSUPPORTED,
+                    "the upsample cascade has no exact frame-rate form (pad frames < its reach, or more than 8 taps)");
+    const int N = kXcdWgs * (path == P_XCD ? kXTerms : kSTerms), state_w = path == P_XCD ? kXStateW : kSStateW;
+    int Tmax = 0;
+    for (int i = 0; i < U; ++i) {
+        const std::string who = "utterance " + std::to_string(i);
+        if (T[i] < 21) return fail(h, WRNN_EINVAL, who + " has " + std::to_string(T[i]) + " frames: fewer than 21 (the fade-out, as wrnn_postprocess)");
+        if ((long long)T[i] * hop > INT_MAX) return fail(h, WRNN_EINVAL, who + ": hop * frames exceeds the step counter");
+        if (!mel[i] || !out[i] || (A4 > 0 && !aux[i])) return fail(h, WRNN_EINVAL, who + ": need mel, aux and out");
+        Tmax = std::max(Tmax, T[i]);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+
+    // ---- the schedule: lanes, then rounds of C lane-steps cut into pieces at utterance boundaries
+    std::vector<int> lane_of(U), pos(U);
+    int64_t lane_frames[kXcds];
+    std::vector<std::vector<int>> queue(lanes);
+    list_plan(T, U, lanes, lane_of.data(), pos.data(), lane_frames, queue.data());
+    long long longest = 0;
+    for (int k = 0; k < lanes; ++k) longest = std::max(longest, (long long)lane_frames[k] * hop);
+    const char *mb_env = std::getenv("WRNN_TERMS_MB");
+    const double budget = (mb_env ? std::atof(mb_env) : 8192.0) * (1 << 20) / 4.0;   // floats
+    const long long C = (long long)std::max(1.0, std::min((double)longest, std::floor(budget / ((double)lanes * N) - 1.0)));
+    const int rounds = (int)((longest + C - 1) / C);
+    struct Piece {
+        int u, t0, Lc, nt;
+    };
+    std::vector<Piece> pcs;
+    std::vector<int> first((size_t)rounds * (kXcds + 1), 0);   // round j, lane k: pieces first[j][k] .. first[j][k + 1]
+    size_t rows_max = 0;
+    for (int j = 0; j < rounds; ++j) {
+        const long long w0 = (long long)j * C, w1 = w0 + C;
+        size_t rows = 0;
+        for (int k = 0; k < kXcds; ++k) {
+            first[(size_t)j * (kXcds + 1) + k] = (int)pcs.size();
+            if (k >= lanes) continue;
+            long long u0 = 0;   // lane-time of the utterance's step 0
+            for (int u : queue[k]) {
+                const long long Lu = (long long)T[u] * hop, a0 = std::max(w0, u0), a1 = std::min(w1, u0 + Lu);
+                if (a1 > a0) {
+                    const int t0 = (int)(a0 - u0), Lc = (int)(a1 - a0);
+                    // the kernels prefetch the terms of the step after the piece while the utterance goes on
+                    const int nt = (int)std::min<long long>(Lc + 1, Lu - t0);
+                    pcs.push_back({u, t0, Lc, nt});
+                    rows += nt;
+                }
+                u0 += Lu;
+            }
+        }
+        first[(size_t)j * (kXcds + 1) + kXcds] = (int)pcs.size();
+        rows_max = std::max(rows_max, rows);
+    }
+
+    // ---- every workspace grown before anything is queued (growing one waits for the device)
+    std::vector<size_t> ft_off(U), at_off(U);
+    size_t arena = 0;
+    for (int i = 0; i < U; ++i) {
+        ft_off[i] = arena;
+        arena += (size_t)(T[i] + nJ - 1) * N;
+        at_off[i] = arena;
+        arena += (size_t)(T[i] + 1) * N;
+    }
+    const int fmax = std::max(Tmax + nJ - 1, Tmax + 1);
+    if (grow(h, h->d_frec, h->frec_cap, (size_t)fmax * h->CD) || grow(h, h->d_X, h->X_cap, (size_t)fmax * h->KXc) ||
+        grow(h, h->d_larena, h->larena_cap, arena) || grow(h, h->d_T, h->T_cap, rows_max * N) ||
+        grow(h, h->d_lstate, h->lstate_cap, (size_t)U * kXcdWgs * state_w))
+        return WRNN_EHIP;
+    HIP_TRY(h, ensure(h->d_lxg, h->lxg_cap, (size_t)U * kXXcdStride));
+    HIP_TRY(h, ensure(h->d_ltab, h->ltab_cap, pcs.size()));
+    if (!h->d_members) HIP_TRY(h, hipMalloc(&h->d_members, kXcds * sizeof(int)));
+    if (!h->ev_ltab) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_ltab, hipEventDisableTiming));
+    HIP_TRY(h, hipEventSynchronize(h->ev_ltab));   // the last call's upload has read the staging copy
+    if (pcs.size() > h->hltab_cap) {
+        if (h->h_ltab) HIP_TRY(h, hipHostFree(h->h_ltab));
+        h->h_ltab = nullptr;
+        h->hltab_cap = 0;
+        HIP_TRY(h, hipHostMalloc((void **)&h->h_ltab, pcs.size() * sizeof(XcdPiece), hipHostMallocDefault));
+        h->hltab_cap = pcs.size();
+    }
+    if (!h->blas && rocblas_create_handle(&h->blas) != rocblas_status_success)
+        return fail(h, WRNN_EHIP, "rocblas_create_handle failed");
+    if (rocblas_set_stream(h->blas, st) != rocblas_status_success) return fail(h, WRNN_EHIP, "rocblas_set_stream failed");
+    if (coef != h->coef_host) {
+        if (grow(h, h->d_coef, h->coef_cap, coef.size())) return WRNN_EHIP;
+        HIP_TRY(h, hipMemcpyAsync(h->d_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipStreamSynchronize(st));   // `coef` is a local: the copy completes before it goes
+        h->coef_host = coef;
+    }
+
+    // ---- the piece table, all rounds at once: one upload, no host wait between rounds
+    for (int j = 0; j < rounds; ++j) {
+        size_t row = 0;   // the round's terms rows so far
+        int blk = 0;      // … and interpolation blocks
+        for (int p = first[(size_t)j * (kXcds + 1)]; p < first[(size_t)j * (kXcds + 1) + kXcds]; ++p) {
+            const Piece &pc = pcs[p];
+            XcdPiece q{};
+            q.r.terms = h->d_T + row * N;
+            q.r.terms_ld = N;
+            q.r.noise = noise ? noise[pc.u] : nullptr;
+            q.r.noise_ld = 11;
+            q.r.out = out[pc.u];
+            q.r.out_t0 = 0;
+            q.r.state = h->d_lstate + (size_t)pc.u * kXcdWgs * state_w;
+            q.r.xg = h->d_lxg + (size_t)pc.u * kXXcdStride;
+            q.r.seed = seed;
+            q.r.row = row_offset + pc.u;
+            q.r.t0 = pc.t0;
+            q.r.Lc = pc.Lc;
+            q.r.L = T[pc.u] * hop;
+            q.r.nz_hor = q.r.L;
+            q.ft = h->d_larena + ft_off[pc.u];
+            q.at = h->d_larena + at_off[pc.u];
+            q.frames = T[pc.u];
+            q.nt = pc.nt;
+            q.blk0 = blk;
+            h->h_ltab[p] = q;
+            row += pc.nt;
+            blk += interp_list_blocks(pc.nt);
+        }
+    }
+
+    // ---- queuing begins
+    HIP_TRY(h, hipMemcpyAsync(h->d_ltab, h->h_ltab, pcs.size() * sizeof(XcdPiece), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipEventRecord(h->ev_ltab, st));
+    HIP_TRY(h, hipMemsetAsync(h->d_lxg, 0, (size_t)U * kXXcdStride * 8, st));   // tags restart at 1 in every utterance
+    HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
+    HIP_TRY(h, hipEventRecord(h->ev0, st));
+    h->last_path = (int)path;
+    // each utterance's frame terms with the launches and shapes of its own wrnn_generate_frames call
+    // (rocBLAS picks its tiling by shape: one GEMM over all utterances would move the last bit)
+    const float one = 1.0f, zero = 0.0f;
+    for (int i = 0; i < U; ++i) {
+        FrameSrc fs;
+        fs.mel = mel[i];
+        fs.aux = aux ? aux[i] : nullptr;
+        fs.U = 1;
+        fs.NF = T[i];
+        fs.hop = hop, fs.nJ = nJ, fs.jlo = jlo;
+        fs.coef = h->d_coef;
+        const int rc = frame_terms(
+            h, fs, N, h->KXc, 0, st,
+            [&](const float *X, int m, float *Cm) -> int {
+                if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, m, h->KXc, &one, h->d_xWt,
+                                  h->KXc, X, h->KXc, &zero, Cm, N) != rocblas_status_success)
+                    return fail(h, WRNN_EHIP, "rocblas_sgemm (frame terms) failed");
+                return WRNN_OK;
+            },
+            h->d_larena + ft_off[i], h->d_larena + at_off[i]);
+        if (rc) return rc;
+    }
+    for (int j = 0; j < rounds; ++j) {
+        const int *f = &first[(size_t)j * (kXcds + 1)];
+        int blocks = 0;
+        for (int p = f[0]; p < f[kXcds]; ++p) blocks += interp_list_blocks(pcs[p].nt);
+        HIP_TRY(h, launch_terms_interp_list(h->d_ltab, f[0], f[kXcds], blocks, h->d_coef, N, hop, nJ, st));
+        HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
+        auto fill = [&](auto &g, const auto &slab) {
+            g.a.slab = h->d_xslab;
+            g.a.members = h->d_members;
+            g.a.ctl = h->d_ctl;
+            g.a.timeout_ticks = h->timeout_ticks;
+            g.a.s = slab;
+            g.a.windowed = 1;
+            g.a.nb = lanes;
+            g.pieces = h->d_ltab;
+            for (int k = 0; k <= kXcds; ++k) g.first[k] = f[k];
+        };
+        if (path == P_XCD) {
+            XcdListArgs g{};
+            fill(g, h->xs);
+            HIP_TRY(h, launch_xcd_list(g, st));
+        } else {
+            XcdsListArgs g{};
+            fill(g, h->xss);
+            HIP_TRY(h, launch_xcds_list(g, st));
+        }
+    }
+    HIP_TRY(h, hipEventRecord(h->ev1, st));
+    h->timed = true;
+    return WRNN_OK;
+}
+
 // ---- streaming sessions (wavernn_amd.h: wrnn_stream_*) ------------------------------------
 // Rows [base, end) of `row` floats each in absolute numbering, appended at `end`; rows behind
 // keep_from may go.  When the live buffer is full the kept rows move to the front of the other one
@@ -3207,8 +3473,11 @@ void wrnn_destroy(wrnn_t *h) {
                     (void *)h->d_members, (void *)h->d_xmslab, (void *)h->d_xmstate, (void *)h->d_xmxg, (void *)h->d_xmnoise,
                     (void *)h->d_xmWt, (void *)h->d_coef, (void *)h->d_FT, (void *)h->d_AT, (void *)h->d_frec,
                     (void *)h->d_cond,
-                    (void *)h->d_dxslab, (void *)h->d_dxstate, (void *)h->d_dxnoise, (void *)h->d_dxxg})
+                    (void *)h->d_dxslab, (void *)h->d_dxstate, (void *)h->d_dxnoise, (void *)h->d_dxxg,
+                    (void *)h->d_larena, (void *)h->d_lstate, (void *)h->d_lxg, (void *)h->d_ltab})
         if (p) (void)hipFree(p);
+    if (h->h_ltab) (void)hipHostFree(h->h_ltab);
+    if (h->ev_ltab) (void)hipEventDestroy(h->ev_ltab);
     if (h->blas) (void)rocblas_destroy_handle(h->blas);
     delete h;
 }

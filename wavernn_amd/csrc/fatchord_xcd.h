@@ -119,6 +119,27 @@ struct XcdGroupArgs {
     XcdRow row[kXcds];
 };
 
+// List launches (wrnn_generate_list): XCD k is a LANE that runs a queue of pieces back to back
+// without leaving the kernel — piece = steps [t0, t0 + Lc) of one utterance, exactly an XcdRow
+// (terms_ld = N: a piece's terms rows are its own, contiguous).  The queue lives in device memory
+// (eight rows already fill ≈ 1 KB of kernel arguments); the interpolation pass that fills a
+// round's terms (terms_interp_list_kernel, frame_terms.hip) walks the same records: ft / at are the
+// utterance's frame-term stores, nt the terms rows of the piece (its steps and, while the
+// utterance goes on, the one after them).  The kernels' kLst instantiation alone reads the table.
+struct XcdPiece {
+    XcdRow r;
+    const float *ft;              // [frames + nJ − 1][N]  W·(mel frame) rows of the utterance
+    const float *at;              // [frames + 1][N]       W·(aux frame, ones) rows
+    int frames, nt;
+    int blk0, pad_;               // the piece's first block of the round's interpolation launch (kInterpSteps rows each)
+};
+
+struct XcdListArgs {
+    XcdArgs a;                    // slab, members, ctl, timeout_ticks, s, nb = lanes; the rest unread
+    const XcdPiece *pieces;       // device: every piece of the call, round-major, lane-major within a round
+    int first[kXcds + 1];         // this launch: XCD k walks pieces first[k] .. first[k + 1] − 1 (none: no XCD)
+};
+
 struct XcdLds {
     int whh1, whh2, h1, h2, sg, w3, f2x, ring, nz, gh2, cst, xs, misc, total;
 };

@@ -89,14 +89,99 @@ namespace wrnn {
                 (unsigned)__builtin_amdgcn_s_memrealtime();                                                   \
     } while (0)
 
+// The set-up of one piece of work inside fatchord_xcd_kernel (the launch's one window; kLst: every piece
+// of the lane's queue — a macro, because the list form needs the text twice and a lambda shared with the
+// other instantiations changes their code): ring slots t0..t0+2, the carried state (the loads consumed by
+// an empty asm use so the wait lands before the loop: left pending, their first use inside it is an
+// s_waitcnt vmcnt(0) in EVERY step, draining all the wave's in-flight publishes and loads there), the
+// GRU1 terms of step 0 (GH1 = 0) published and gathered, x_{t-1} and the GRU1 terms of the first step.
+// Returns from the kernel when the launch was aborted.
+#define XCD_PIECE_BEGIN()                                                                                     \
+    do {                                                                                                      \
+        {                                                                                                     \
+            for (int t = t0; t < t0 + 3; ++t) {                                                               \
+                if (t <= t_terms)                                                                             \
+                    for (int i = tid; i < kXTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];                  \
+                if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);                        \
+            }                                                                                                 \
+        }                                                                                                     \
+        resume = t0 > 0;                                                                                      \
+        if constexpr (kGrp) st = rw.state + (size_t)c * kXStateW;                                             \
+        else st = a.state + ((size_t)k * kXcdWgs + c) * kXStateW;                                             \
+        h1v = resume ? st[tid] : 0.0f;                                                                        \
+        h2own = resume ? st[512 + 2048 + 48 + ui] : 0.0f;                                                     \
+        asm volatile("" : "+v"(h1v), "+v"(h2own));                                                            \
+        if (resume) {                                                                                         \
+            for (int i = tid; i < 4 * R; i += kXThreads) sg[i] = st[512 + i];                                 \
+            if (tid < 48) gh2s[tid] = st[512 + 2048 + tid];                                                   \
+            if (tid == 0) xs[(t0 + 1) & 1] = st[512 + 2048 + 48 + 16];                                        \
+        } else {                                                                                              \
+            if (tid < 48) gh2s[tid] = 0.0f;                                                                   \
+            if (tid == 0) xs[1] = 0.0f;                                                                       \
+        }                                                                                                     \
+        __syncthreads();                                                                                      \
+        if (!resume) {                                                                                        \
+            if (gh1w) {                                                                                       \
+                const float z5[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};                                           \
+                publish_terms(0, z5);                                                                         \
+            }                                                                                                 \
+            if (wave == 1 || wave == 2 || wave == 5 || wave == WRNN_XCD_SQ3_WAVE) {                           \
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                              \
+                gather_terms(0);                                                                              \
+            }                                                                                                 \
+        }                                                                                                     \
+        __syncthreads();                                                                                      \
+        if (*abort_flag) return;                                                                              \
+        x = xs[(t0 + 1) & 1];                                                                                 \
+        s4 = lds4(sg + 4 * tid);                                                                              \
+    } while (0)
+
+// … and its end: the recurrent state carried to the next time chunk (every workgroup its own copy)
+#define XCD_PIECE_END()                                                                                       \
+    do {                                                                                                      \
+        __syncthreads();                                                                                      \
+        st[tid] = h1v;                                                                                        \
+        for (int i = tid; i < 4 * R; i += kXThreads) st[512 + i] = sg[i];                                     \
+        if (tid < 48) st[512 + 2048 + tid] = gh2s[tid];                                                       \
+        if (g2w && li < 2) st[512 + 2048 + 48 + ui] = h2own;                                                  \
+        if (tid == 0) st[512 + 2048 + 48 + 16] = xs[(t_end - 1) & 1];                                         \
+    } while (0)
+
 __device__ __forceinline__ const XcdArgs &launch_args(const XcdArgs &ka) { return ka; }
 __device__ __forceinline__ const XcdArgs &launch_args(const XcdGroupArgs &ka) { return ka.a; }
+__device__ __forceinline__ const XcdArgs &launch_args(const XcdListArgs &ka) { return ka.a; }
 
 // kGrp (grouped launches, fatchord_xcd.h: XcdRow): the row's window, operands and results come from
 // row k of the table instead of the launch-wide fields; the steps themselves are the same code
-template <bool kDbg, bool kWin, bool kGrp = false>
-__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditional_t<kGrp, XcdGroupArgs, XcdArgs> ka) {
+// kLst (list launches, fatchord_xcd.h: XcdPiece; a kGrp whose row changes): XCD k walks a queue of
+// pieces in device memory.  Membership and the resident weights are set up once per launch; per
+// piece only the window, the operand bases, the ring and the state — and the step loop runs as it is.
+//
+// Tags at a piece boundary.  Every tagged word carries step + 1 of the utterance it serves, and a
+// new utterance restarts at step 0, so a word left by the previous piece could pass for one of the
+// next piece's steps.  Neither kind can:
+//   * hand-off granules (global): an utterance has a granule region of its own, zeroed before the
+//     call and kept across its rounds.  Consecutive pieces of a lane within one launch belong to
+//     DIFFERENT utterances (a piece ends where its utterance or the round ends), so a step of piece
+//     B polls only words that B's own steps wrote, or zero; the tags an utterance left in an
+//     earlier round are those of steps before t0 (the GRU1 terms of step t0 come back from the
+//     state record, not from a gather), below every tag the resumed piece waits for — a session's
+//     chunks rely on the same.
+//     For the same reason no barrier spans the XCD at a boundary: a workgroup already in B and one
+//     still in A touch disjoint regions, and B's first hand-off waits for B's publishers as any
+//     step does.  The state record is per workgroup (each reads and writes its own slice only).
+//   * LDS words (misc[2..7], the f2x pairs): all waves of the workgroup pass the barrier behind
+//     the piece's last step, store the state, pass a second barrier (nobody reads the old piece's
+//     LDS any more), then the words are zeroed — tag 0, which no step carries — ahead of the
+//     barrier that precedes the new piece's first flag wait.
+// The launch runs ONE step loop over the lane's time: the piece switch is a cold block at the end
+// of a piece's last step.  A piece loop around the step loop kept the lane-invariant part AND the
+// per-piece sum of every per-lane address alive across the steps and spilled into the step.
+template <bool kDbg, bool kWin, bool kGrp = false, bool kLst = false>
+__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
+    std::conditional_t<kLst, XcdListArgs, std::conditional_t<kGrp, XcdGroupArgs, XcdArgs>> ka) {
     static_assert(!kGrp || (kWin && !kDbg), "grouped launches are windowed and carry no stamps");
+    static_assert(!kLst || kGrp, "a list launch is a grouped one whose rows come from the piece queue");
     const XcdArgs &a = launch_args(ka);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int R = 512, TW = kXcdWgs * kXTerms;
@@ -113,7 +198,11 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditi
     if (tid == 0) {
         const int k = (int)xcc_id();
         int c = kXcdWgs;
-        if constexpr (kGrp) {   // a row without steps takes no XCD: its workgroups leave here
+        if constexpr (kLst) {   // a lane whose timeline has ended takes no XCD
+            const bool in = k < a.nb && ka.first[k + 1] > ka.first[k];
+            if (in) c = atomicAdd(&a.members[k], 1);
+            misc[1] = (in && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        } else if constexpr (kGrp) {   // a row without steps takes no XCD: its workgroups leave here
             const bool in = k < a.nb && ka.row[k].Lc > 0;
             if (in) c = atomicAdd(&a.members[k], 1);
             misc[1] = (in && c < kXcdWgs) ? k * kXcdWgs + c : -1;
@@ -132,8 +221,16 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditi
     const int b = a.b0 + k;
     // the row's step window: the launch's, or (kGrp) its own — k is wave-uniform, the table reads scalar
     int t0, Lc, L;
-    XcdRow rw{};   // kGrp: row k of the table, read once here
-    if constexpr (kGrp) {
+    XcdRow rw{};   // kGrp: row k of the table, read once here; kLst: the piece being run
+    [[maybe_unused]] int pi = 0, pend = 0;   // kLst: the lane's queue position and end
+    if constexpr (kLst) {
+        pi = ka.first[k];
+        pend = ka.first[k + 1];
+        rw = list_piece<XcdRow>(ka.pieces, pi);
+        t0 = rw.t0;
+        Lc = rw.Lc;
+        L = rw.L;
+    } else if constexpr (kGrp) {
         rw = ka.row[k];
         t0 = rw.t0;
         Lc = rw.Lc;
@@ -143,8 +240,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditi
         Lc = a.Lc;
         L = a.L;
     }
-    const int t_end = t0 + Lc;
-    const int t_terms = min(t_end, L - 1);
+    int t_end = t0 + Lc;
+    int t_terms = min(t_end, L - 1);
     int nz_hor;   // the step below which injected draws exist
     if constexpr (kGrp) nz_hor = rw.nz_hor;
     else nz_hor = kWin ? a.nz_hor : L;
@@ -155,7 +252,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditi
     // publishes through one wave-uniform buffer descriptor + a 32-bit granule index (the 64-bit
     // per-lane pointers of each hop stayed live across the loop and were spilled: the F2 publish
     // reloaded its address from scratch and waited vmcnt(0) on the critical path)
-    const __amdgpu_buffer_rsrc_t xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);
+    __amdgpu_buffer_rsrc_t xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);
     auto XGI = [&](int hop) { return hop * (int)kXHopStride; };
     auto RING = [&](int t) { return ring + (t & (kXRing - 1)) * kXTerms; };
     auto NZ = [&](int t) { return nzr + (t & (kXRing - 1)) * kXNoise; };
@@ -328,47 +425,19 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditi
         for (int i = tid; i < kXH2LdsRows * R / 4; i += kXThreads) dst[i] = src[i];
         for (int i = tid; i < kXFcRows * 32; i += kXThreads) w3s[i] = S[a.s.w3 + i];
         for (int i = tid; i < kXCst; i += kXThreads) cst[i] = S[a.s.cst + i];
-        for (int t = t0; t < t0 + 3; ++t) {
-            if (t <= t_terms)
-                for (int i = tid; i < kXTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];
-            if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);
-        }
     }
-    const bool resume = t0 > 0;
+    // ---- per piece of work (the launch's one window; kLst: every piece of the lane's queue): ring
+    // slots t0..t0+2, the carried state, the step-0 terms; afterwards the state store
+    bool resume;
     float *st;
-    if constexpr (kGrp) st = rw.state + (size_t)c * kXStateW;
-    else st = a.state + ((size_t)k * kXcdWgs + c) * kXStateW;
-    float h1v = resume ? st[tid] : 0.0f;              // h1 of unit tid (recurrent, this thread)
-    float h2own = resume ? st[512 + 2048 + 48 + ui] : 0.0f;   // h2 of this lane's GRU2 unit (GRU2 waves)
-    // consume the carried-state loads here (an empty asm use: the wait lands before the loop);
-    // left pending into the loop, their first use inside it is an s_waitcnt vmcnt(0) in EVERY
-    // step (GRU1's h1 update), draining all the wave's in-flight publishes and loads there
-    asm volatile("" : "+v"(h1v), "+v"(h2own));
-    if (resume) {
-        for (int i = tid; i < 4 * R; i += kXThreads) sg[i] = st[512 + i];
-        if (tid < 48) gh2s[tid] = st[512 + 2048 + tid];
-        if (tid == 0) xs[(t0 + 1) & 1] = st[512 + 2048 + 48 + 16];
-    } else {
-        if (tid < 48) gh2s[tid] = 0.0f;
-        if (tid == 0) xs[1] = 0.0f;
-    }
-    __syncthreads();
-    if (!resume) {   // GRU1 terms of step 0 (GH1 = 0), published and gathered
-        if (gh1w) {
-            const float z5[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            publish_terms(0, z5);
-        }
-        if (wave == 1 || wave == 2 || wave == 5 || wave == WRNN_XCD_SQ3_WAVE) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            gather_terms(0);
-        }
-    }
-    __syncthreads();
-    if (*abort_flag) return;
+    float h1v, h2own;   // h1 of unit tid (recurrent, this thread); h2 of this lane's GRU2 unit (GRU2 waves)
+    float x;            // x_{t-1}, wave-uniform
+    f4v s4;             // GRU1 terms of unit tid for step t
+    XCD_PIECE_BEGIN();
 
     if (WRNN_XCD_PRIO && wave == 0) __builtin_amdgcn_s_setprio(WRNN_XCD_PRIO);
-    float x = xs[(t0 + 1) & 1];                    // x_{t-1}, wave-uniform
-    f4v s4 = lds4(sg + 4 * tid);                     // GRU1 terms of unit tid for step t
+    // kLst: ONE step loop over the lane's time in this launch — the piece switch sits in a cold
+    // block at its end, so nothing of a piece's set-up lives in registers across the steps
     for (int t = t0; t < t_end; ++t) {
         const uint32_t tag = (uint32_t)t + 1u;
         const bool more = t + 1 < L;
@@ -693,20 +762,41 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(std::conditi
         s4 = lds4(sg + 4 * tid);
         if (ab) return;
         if (wave != 0) x = xn;
+        if constexpr (kLst) {
+            if (t + 1 == t_end) {
+                // ---- the lane's next piece: the state store, then its window, bases and descriptor;
+                // the LDS tags back to 0 behind a barrier (the state store was the last reader of the
+                // old piece's LDS), ahead of the barrier that follows the new piece's state set-up
+                // (the argument stands above the kernel)
+                XCD_PIECE_END();
+                if (++pi >= pend) return;
+                rw = list_piece<XcdRow>(ka.pieces, pi);
+                t0 = rw.t0;
+                Lc = rw.Lc;
+                L = rw.L;
+                t_end = t0 + Lc;
+                t_terms = min(t_end, L - 1);
+                nz_hor = rw.nz_hor;
+                xg = rw.xg;
+                xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);
+                prow = (unsigned long long)rw.row;
+                seed = rw.seed;
+                __syncthreads();
+                if (tid < 64) f2x[tid] = 0.0f;
+                if (tid >= 64 && tid < 70) misc[tid - 62] = 0;
+                XCD_PIECE_BEGIN();
+                t = t0 - 1;
+            }
+        }
     }
-    // ---- carry the recurrent state to the next time chunk (every workgroup its own copy)
-    __syncthreads();
-    st[tid] = h1v;
-    for (int i = tid; i < 4 * R; i += kXThreads) st[512 + i] = sg[i];
-    if (tid < 48) st[512 + 2048 + tid] = gh2s[tid];
-    if (g2w && li < 2) st[512 + 2048 + 48 + ui] = h2own;
-    if (tid == 0) st[512 + 2048 + 48 + 16] = xs[(t_end - 1) & 1];
+    if constexpr (!kLst) XCD_PIECE_END();
 }
 
 #define WRNN_K_XCD fatchord_xcd_kernel<false, false>
 #define WRNN_K_XCD_DBG fatchord_xcd_kernel<true, false>
 #define WRNN_K_XCD_WIN fatchord_xcd_kernel<false, true>   // streaming sessions (no stamps)
 #define WRNN_K_XCD_GRP fatchord_xcd_kernel<false, true, true>   // group pushes: a window per row
+#define WRNN_K_XCD_LST fatchord_xcd_kernel<false, true, true, true>   // list launches: a queue of pieces per XCD
 
 hipError_t launch_xcd(const XcdArgs &a, hipStream_t st) {
     XcdArgs args = a;
@@ -722,9 +812,16 @@ hipError_t launch_xcd_group(const XcdGroupArgs &g, hipStream_t st) {
                            xcd_lds_layout().total * sizeof(float), st);
 }
 
+hipError_t launch_xcd_list(const XcdListArgs &g, hipStream_t st) {
+    XcdListArgs args = g;
+    void *params[] = {&args};
+    return hipLaunchKernel((const void *)WRNN_K_XCD_LST, dim3(kXcds * kXcdWgs), dim3(kXThreads), params,
+                           xcd_lds_layout().total * sizeof(float), st);
+}
+
 hipError_t prepare_xcd_kernel(int max_lds_bytes) {
     for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN,
-                           (const void *)WRNN_K_XCD_GRP}) {
+                           (const void *)WRNN_K_XCD_GRP, (const void *)WRNN_K_XCD_LST}) {
         hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
         if (e != hipSuccess) return e;
     }
@@ -734,7 +831,7 @@ hipError_t prepare_xcd_kernel(int max_lds_bytes) {
 hipError_t xcd_occupancy(int *blocks_per_cu) {
     int best = 1 << 30;
     for (const void *kf : {(const void *)WRNN_K_XCD, (const void *)WRNN_K_XCD_DBG, (const void *)WRNN_K_XCD_WIN,
-                           (const void *)WRNN_K_XCD_GRP}) {
+                           (const void *)WRNN_K_XCD_GRP, (const void *)WRNN_K_XCD_LST}) {
         int n = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kf, kXThreads, xcd_lds_layout().total * sizeof(float));
         if (e != hipSuccess) return e;

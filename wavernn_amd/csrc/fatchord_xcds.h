@@ -76,6 +76,13 @@ struct XcdsGroupArgs {
     XcdRow row[kXcds];
 };
 
+// List launches (fatchord_xcd.h: XcdPiece, XcdListArgs), the same queue for this kernel
+struct XcdsListArgs {
+    XcdsArgs a;                   // slab, members, ctl, timeout_ticks, s, nb = lanes; the rest unread
+    const XcdPiece *pieces;
+    int first[kXcds + 1];
+};
+
 struct XcdsLds {
     int h1, h2, sg, w3, f2x, ring, nz, gh2, cst, xs, misc, whh1b, whh1c, whh2b, whh2c, total;
 };

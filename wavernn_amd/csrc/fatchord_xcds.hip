@@ -175,14 +175,77 @@ __device__ __forceinline__ float sp_block_row(const f4v (&wa)[4], const f4v (&wb
                 (unsigned)__builtin_amdgcn_s_memrealtime();                                                   \
     } while (0)
 
+// The set-up of one piece of work inside fatchord_xcds_kernel and its end, as fatchord_xcd.hip's
+// XCD_PIECE_BEGIN / XCD_PIECE_END (macros: the list form needs the text twice): ring slots t0..t0+2,
+// wave 7's staged ring entries of t0+3, the carried state, the GRU1 terms of step 0 (GH1 = 0) published
+// and gathered, x_{t-1} and the GRU1 terms of the first step; returns from the kernel on an abort.
+#define XCDS_PIECE_BEGIN()                                                                                    \
+    do {                                                                                                      \
+        for (int t = t0; t < t0 + 3; ++t) {                                                                   \
+            if (t <= t_terms)                                                                                 \
+                for (int i = tid; i < kSTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];                      \
+            if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);                            \
+        }                                                                                                     \
+        if (wave == 7) stage_ring(t0 + 3);                                                                    \
+        resume = t0 > 0;                                                                                      \
+        if constexpr (kGrp) st = rw.state + (size_t)c * kSStateW;                                             \
+        else st = a.state + ((size_t)k * kXcdWgs + c) * kSStateW;                                             \
+        h1v = resume ? st[tid] : 0.0f;                                                                        \
+        h1v2 = (resume && two) ? st[u2] : 0.0f;                                                               \
+        h2own = resume ? st[oH2 + ul] : 0.0f;                                                                 \
+        if (resume) {                                                                                         \
+            for (int i = tid; i < 4 * R; i += kXThreads) sg[i] = st[oSG + i];                                 \
+            if (tid < 84) gh2s[tid] = st[oGH2 + tid];                                                         \
+            if (tid == 0) xs[(t0 + 1) & 1] = st[oX];                                                          \
+        } else {                                                                                              \
+            if (tid < 84) gh2s[tid] = 0.0f;                                                                   \
+            if (tid == 0) xs[1] = 0.0f;                                                                       \
+        }                                                                                                     \
+        __syncthreads();                                                                                      \
+        if (!resume) {                                                                                        \
+            if (wave < 4) {                                                                                   \
+                publish_terms(0, br0, 0.0f);                                                                  \
+                publish_terms(0, br1, 0.0f);                                                                  \
+            }                                                                                                 \
+            if (sq_of(wave) >= 0) {                                                                           \
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                              \
+                gather_terms(0);                                                                              \
+            }                                                                                                 \
+        }                                                                                                     \
+        __syncthreads();                                                                                      \
+        if (*abort_flag) return;                                                                              \
+        x = xs[(t0 + 1) & 1];                                                                                 \
+        s4 = lds4(sg + 4 * tid);                                                                              \
+        s4b = lds4(sg + 4 * u2);                                                                              \
+    } while (0)
+
+// … the recurrent state carried to the next time chunk (every workgroup its own copy)
+#define XCDS_PIECE_END()                                                                                      \
+    do {                                                                                                      \
+        __syncthreads();                                                                                      \
+        st[tid] = h1v;                                                                                        \
+        if (two) st[u2] = h1v2;                                                                               \
+        for (int i = tid; i < 4 * R; i += kXThreads) st[oSG + i] = sg[i];                                     \
+        if (tid < 84) st[oGH2 + tid] = gh2s[tid];                                                             \
+        if (wave < kSUB && lane < 4) st[oH2 + ul] = h2own;                                                    \
+        if (tid == 0) st[oX] = xs[(t_end - 1) & 1];                                                           \
+    } while (0)
+
 __device__ __forceinline__ const XcdsArgs &launch_args(const XcdsArgs &ka) { return ka; }
 __device__ __forceinline__ const XcdsArgs &launch_args(const XcdsGroupArgs &ka) { return ka.a; }
+__device__ __forceinline__ const XcdsArgs &launch_args(const XcdsListArgs &ka) { return ka.a; }
 
 // kGrp (grouped launches, fatchord_xcd.h: XcdRow): the row's window, operands and results come from
 // row k of the table instead of the launch-wide fields; the steps themselves are the same code
-template <bool kDbg, bool kWin, bool kGrp = false>
-__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::conditional_t<kGrp, XcdsGroupArgs, XcdsArgs> ka) {
+// kLst (list launches): as fatchord_xcd_kernel's — XCD k walks a queue of pieces in device memory,
+// membership and the resident weights once per launch, ONE step loop with the piece switch in a cold
+// block at its end; the tag argument stands above that kernel (here the LDS words are misc[2..7] and
+// the three waves' fc3 hand-off pairs; wave 7 restages its ring registers at every piece start)
+template <bool kDbg, bool kWin, bool kGrp = false, bool kLst = false>
+__global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(
+    std::conditional_t<kLst, XcdsListArgs, std::conditional_t<kGrp, XcdsGroupArgs, XcdsArgs>> ka) {
     static_assert(!kGrp || (kWin && !kDbg), "grouped launches are windowed and carry no stamps");
+    static_assert(!kLst || kGrp, "a list launch is a grouped one whose rows come from the piece queue");
     const XcdsArgs &a = launch_args(ka);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int R = kSR, TW = kXcdWgs * kSTerms;
@@ -202,7 +265,11 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::condit
     if (tid == 0) {
         const int k = (int)xcc_id();
         int c = kXcdWgs;
-        if constexpr (kGrp) {   // a row without steps takes no XCD: its workgroups leave here
+        if constexpr (kLst) {   // a lane whose timeline has ended takes no XCD
+            const bool in = k < a.nb && ka.first[k + 1] > ka.first[k];
+            if (in) c = atomicAdd(&a.members[k], 1);
+            misc[1] = (in && c < kXcdWgs) ? k * kXcdWgs + c : -1;
+        } else if constexpr (kGrp) {   // a row without steps takes no XCD: its workgroups leave here
             const bool in = k < a.nb && ka.row[k].Lc > 0;
             if (in) c = atomicAdd(&a.members[k], 1);
             misc[1] = (in && c < kXcdWgs) ? k * kXcdWgs + c : -1;
@@ -221,8 +288,16 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::condit
     const int b = a.b0 + k;
     // the row's step window: the launch's, or (kGrp) its own — k is wave-uniform, the table reads scalar
     int t0, Lc, L;
-    XcdRow rw{};   // kGrp: row k of the table, read once here
-    if constexpr (kGrp) {
+    XcdRow rw{};   // kGrp: row k of the table, read once here; kLst: the piece being run
+    [[maybe_unused]] int pi = 0, pend = 0;   // kLst: the lane's queue position and end
+    if constexpr (kLst) {
+        pi = ka.first[k];
+        pend = ka.first[k + 1];
+        rw = list_piece<XcdRow>(ka.pieces, pi);
+        t0 = rw.t0;
+        Lc = rw.Lc;
+        L = rw.L;
+    } else if constexpr (kGrp) {
         rw = ka.row[k];
         t0 = rw.t0;
         Lc = rw.Lc;
@@ -232,8 +307,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::condit
         Lc = a.Lc;
         L = a.L;
     }
-    const int t_end = t0 + Lc;
-    const int t_terms = min(t_end, L - 1);
+    int t_end = t0 + Lc;
+    int t_terms = min(t_end, L - 1);
     int nz_hor;   // the step below which injected draws exist
     if constexpr (kGrp) nz_hor = rw.nz_hor;
     else nz_hor = kWin ? a.nz_hor : L;
@@ -249,7 +324,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::condit
         else return nzp[((size_t)t * a.Bt + b) * 11 + lane_];
     };
     auto XG = [&](int hop) { return xg + (size_t)hop * kXHopStride; };
-    const __amdgpu_buffer_rsrc_t xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);   // publishes
+    __amdgpu_buffer_rsrc_t xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);   // publishes
     auto XGI = [&](int hop) { return hop * (int)kXHopStride; };                                          // granule index
     auto RING = [&](int t) { return ring + (t & (kXRing - 1)) * kSTerms; };
     auto NZ = [&](int t) { return nzr + (t & (kXRing - 1)) * kXNoise; };
@@ -409,11 +484,6 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::condit
         }
         for (int i = tid; i < kXFcRows * 32; i += kXThreads) w3s[i] = S[a.s.w3 + i];
         for (int i = tid; i < kSCst; i += kXThreads) cst[i] = S[a.s.cst + i];
-        for (int t = t0; t < t0 + 3; ++t) {
-            if (t <= t_terms)
-                for (int i = tid; i < kSTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];
-            if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);
-        }
     }
     // wave 7 stages the ring entries of a step in wg (its GRU2 registers, unused by wave 7):
     // conditioning terms (lanes < 57, one float4 each) and the injected sampler noise (lanes < 11)
@@ -421,39 +491,15 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::condit
         if (t <= t_terms && lane < kSTerms / 4) wg[0] = reinterpret_cast<const f4v *>(TERMS(t))[lane];
         if (nzp && t < nz_hor && lane < 11) wg[1].x = DRAW(t, lane);
     };
-    if (wave == 7) stage_ring(t0 + 3);
-    const bool resume = t0 > 0;
-    float *st;
-    if constexpr (kGrp) st = rw.state + (size_t)c * kSStateW;
-    else st = a.state + ((size_t)k * kXcdWgs + c) * kSStateW;
     constexpr int oSG = kSR, oGH2 = kSR + 4 * kSR, oH2 = oGH2 + 84, oX = oH2 + kSU;
-    float h1v = resume ? st[tid] : 0.0f;               // h1 of units tid, tid + 512 (this thread)
-    float h1v2 = (resume && two) ? st[u2] : 0.0f;
-    float h2own = resume ? st[oH2 + ul] : 0.0f;       // h2 of unit ul (lanes 0..3 of waves 0..6)
-    if (resume) {
-        for (int i = tid; i < 4 * R; i += kXThreads) sg[i] = st[oSG + i];
-        if (tid < 84) gh2s[tid] = st[oGH2 + tid];
-        if (tid == 0) xs[(t0 + 1) & 1] = st[oX];
-    } else {
-        if (tid < 84) gh2s[tid] = 0.0f;
-        if (tid == 0) xs[1] = 0.0f;
-    }
-    __syncthreads();
-    if (!resume) {   // GRU1 terms of step 0 (GH1 = 0), published and gathered
-        if (wave < 4) {
-            publish_terms(0, br0, 0.0f);
-            publish_terms(0, br1, 0.0f);
-        }
-        if (sq_of(wave) >= 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            gather_terms(0);
-        }
-    }
-    __syncthreads();
-    if (*abort_flag) return;
+    bool resume;
+    float *st;
+    float h1v, h1v2;   // h1 of units tid, tid + 512 (this thread)
+    float h2own;       // h2 of unit ul (lanes 0..3 of waves 0..6)
+    float x;           // x_{t-1}, wave-uniform
+    f4v s4, s4b;
+    XCDS_PIECE_BEGIN();
 
-    float x = xs[(t0 + 1) & 1];                    // x_{t-1}, wave-uniform
-    f4v s4 = lds4(sg + 4 * tid), s4b = lds4(sg + 4 * u2);
     for (int t = t0; t < t_end; ++t) {
         const uint32_t tag = (uint32_t)t + 1u;
         const bool more = t + 1 < L;
@@ -706,21 +752,40 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcds_kernel(std::condit
         s4b = lds4(sg + 4 * u2);
         if (ab) return;
         if (wave != 0) x = xn;
+        if constexpr (kLst) {
+            if (t + 1 == t_end) {
+                // ---- the lane's next piece (as fatchord_xcd_kernel's): the state store, the new window,
+                // bases and descriptor, the LDS tags back to 0 between two barriers, the set-up
+                XCDS_PIECE_END();
+                if (++pi >= pend) return;
+                rw = list_piece<XcdRow>(ka.pieces, pi);
+                t0 = rw.t0;
+                Lc = rw.Lc;
+                L = rw.L;
+                t_end = t0 + Lc;
+                t_terms = min(t_end, L - 1);
+                nz_hor = rw.nz_hor;
+                xg = rw.xg;
+                nzp = rw.noise;
+                xgr = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 0x7fffffff, 0x00020000);
+                prow = (unsigned long long)rw.row;
+                seed = rw.seed;
+                __syncthreads();
+                if (tid < 3 * 64) f2x[tid] = 0.0f;
+                if (tid >= 3 * 64 && tid < 3 * 64 + 6) misc[tid - 3 * 64 + 2] = 0;
+                XCDS_PIECE_BEGIN();
+                t = t0 - 1;
+            }
+        }
     }
-    // ---- carry the recurrent state to the next time chunk (every workgroup its own copy)
-    __syncthreads();
-    st[tid] = h1v;
-    if (two) st[u2] = h1v2;
-    for (int i = tid; i < 4 * R; i += kXThreads) st[oSG + i] = sg[i];
-    if (tid < 84) st[oGH2 + tid] = gh2s[tid];
-    if (wave < kSUB && lane < 4) st[oH2 + ul] = h2own;
-    if (tid == 0) st[oX] = xs[(t_end - 1) & 1];
+    if constexpr (!kLst) XCDS_PIECE_END();
 }
 
 #define WRNN_K_XCDS fatchord_xcds_kernel<false, false>
 #define WRNN_K_XCDS_DBG fatchord_xcds_kernel<true, false>
 #define WRNN_K_XCDS_WIN fatchord_xcds_kernel<false, true>   // streaming sessions (no stamps)
 #define WRNN_K_XCDS_GRP fatchord_xcds_kernel<false, true, true>   // group pushes: a window per row
+#define WRNN_K_XCDS_LST fatchord_xcds_kernel<false, true, true, true>   // list launches: a queue of pieces per XCD
 
 hipError_t launch_xcds(const XcdsArgs &a, hipStream_t st) {
     XcdsArgs args = a;
@@ -736,9 +801,16 @@ hipError_t launch_xcds_group(const XcdsGroupArgs &g, hipStream_t st) {
                            xcds_lds_layout().total * sizeof(float), st);
 }
 
+hipError_t launch_xcds_list(const XcdsListArgs &g, hipStream_t st) {
+    XcdsListArgs args = g;
+    void *params[] = {&args};
+    return hipLaunchKernel((const void *)WRNN_K_XCDS_LST, dim3(kXcds * kXcdWgs), dim3(kXThreads), params,
+                           xcds_lds_layout().total * sizeof(float), st);
+}
+
 hipError_t prepare_xcds_kernel(int max_lds_bytes) {
     for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN,
-                           (const void *)WRNN_K_XCDS_GRP}) {
+                           (const void *)WRNN_K_XCDS_GRP, (const void *)WRNN_K_XCDS_LST}) {
         hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
         if (e != hipSuccess) return e;
     }
@@ -748,7 +820,7 @@ hipError_t prepare_xcds_kernel(int max_lds_bytes) {
 hipError_t xcds_occupancy(int *blocks_per_cu) {
     int best = 1 << 30;
     for (const void *kf : {(const void *)WRNN_K_XCDS, (const void *)WRNN_K_XCDS_DBG, (const void *)WRNN_K_XCDS_WIN,
-                           (const void *)WRNN_K_XCDS_GRP}) {
+                           (const void *)WRNN_K_XCDS_GRP, (const void *)WRNN_K_XCDS_LST}) {
         int n = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kf, kXThreads, xcds_lds_layout().total * sizeof(float));
         if (e != hipSuccess) return e;

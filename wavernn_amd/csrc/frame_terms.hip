@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fatchord_xcd.h"
+
 namespace wrnn {
 
 // Frame-level conditioning records [frames][U][CD] for the path's own GEMM-input packer
@@ -185,6 +187,85 @@ hipError_t launch_terms_interp_win(const float *FT, int ft_base, const float *AT
     hipLaunchKernelGGL(terms_interp_win_kernel, grid, dim3(kInterpThreads), 0, st, a);
     return hipGetLastError();
 }
+
+// ---- list launches (wrnn_generate_list): the same pass for every piece of one round -------------
+// Pieces p0 .. p1 − 1 of the device piece table (fatchord_xcd.h: XcdPiece) are the round's; piece p
+// is steps [r.t0, r.t0 + nt) of one unbatched utterance (U = 1, nf = 1: the frame-row stride is N),
+// its terms rows contiguous at r.terms, its frame rows at ft / at.  A step of an unbatched loop
+// lies inside its utterance, and for a given (utterance, step) the sum runs in
+// terms_interp_kernel's order: acc = AT[f], then fmaf(coef[φ][j], FT[f + j], acc) for j = 0 .. nJ − 1.
+// blockIdx.x counts the kInterpSteps-step blocks of the pieces in table order (piece p: from blk0 on).
+struct InterpListArgs {
+    const XcdPiece *pieces;
+    const float *coef;    // [hop][nJ]
+    int p0, p1;
+    int N, hop, nJ;
+};
+
+__global__ __launch_bounds__(kInterpThreads) void terms_interp_list_kernel(InterpListArgs a) {
+    const int c4 = blockIdx.y * kInterpThreads + threadIdx.x;   // float4 column
+    if (4 * c4 >= a.N) return;
+    // the piece of this block: the last one whose first block (blk0, written by the host) is not past it
+    int lo = a.p0, hi = a.p1 - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.pieces[mid].blk0 <= (int)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const int p = lo, blk = (int)blockIdx.x - a.pieces[p].blk0;
+    if (blk * kInterpSteps >= a.pieces[p].nt) return;
+    const XcdPiece &pc = a.pieces[p];
+    const int nt = pc.nt, NF = pc.frames, s0 = pc.r.t0, tb = blk * kInterpSteps;
+    const int L_utt = NF * a.hop;
+    const size_t rs = (size_t)a.N;                               // frame-row stride (one utterance)
+    const float *A0 = pc.at + 4 * c4, *F0 = pc.ft + 4 * c4;
+    float *T = const_cast<float *>(pc.r.terms);
+    float4 fr[kInterpMaxJ], ar = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int loaded = -1;
+    for (int i = 0; i < kInterpSteps; ++i) {
+        const int tl = tb + i;
+        if (tl >= nt) break;
+        const int ps = s0 + tl;
+        const int f = ps < L_utt ? ps / a.hop : NF;
+        if (f != loaded) {
+            ar = *reinterpret_cast<const float4 *>(A0 + (size_t)f * rs);
+            if (f < NF) {
+#pragma unroll
+                for (int j = 0; j < kInterpMaxJ; ++j)
+                    if (j < a.nJ) fr[j] = *reinterpret_cast<const float4 *>(F0 + (size_t)(f + j) * rs);
+            }
+            loaded = f;
+        }
+        float4 acc = ar;
+        if (f < NF) {
+            const float *cf = a.coef + (size_t)(ps - f * a.hop) * a.nJ;
+#pragma unroll
+            for (int j = 0; j < kInterpMaxJ; ++j) {
+                if (j < a.nJ) {
+                    const float w = cf[j];
+                    acc.x = fmaf(w, fr[j].x, acc.x);
+                    acc.y = fmaf(w, fr[j].y, acc.y);
+                    acc.z = fmaf(w, fr[j].z, acc.z);
+                    acc.w = fmaf(w, fr[j].w, acc.w);
+                }
+            }
+        }
+        *reinterpret_cast<float4 *>(T + (size_t)tl * a.N + 4 * c4) = acc;
+    }
+}
+
+// `blocks` = Σ ⌈nt_p / kInterpSteps⌉ over the round's pieces (the host knows every nt);
+// N % 4 == 0 and nJ <= kInterpMaxJ as above
+hipError_t launch_terms_interp_list(const XcdPiece *pieces, int p0, int p1, int blocks, const float *coef, int N, int hop,
+                                    int nJ, hipStream_t st) {
+    if (blocks <= 0) return hipSuccess;
+    InterpListArgs a{pieces, coef, p0, p1, N, hop, nJ};
+    const dim3 grid(blocks, (N / 4 + kInterpThreads - 1) / kInterpThreads);
+    hipLaunchKernelGGL(terms_interp_list_kernel, grid, dim3(kInterpThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+int interp_list_blocks(int nt) { return (nt + kInterpSteps - 1) / kInterpSteps; }
 
 // The MelResNet input of a session's newly computable aux frames, and its carried mel tail, in one
 // pass.  Frame g of the running mel is 0 outside [0, R_old + n) (pad_tensor's zeros: before the

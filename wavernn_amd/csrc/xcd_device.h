@@ -354,4 +354,20 @@ __device__ __forceinline__ void fc8_rows(const f4v (&w)[16], const f2v (&xk)[4],
     }
 }
 
+// Piece i of a list launch's queue (fatchord_xcd.h: XcdPiece, its XcdRow `r`), wave-uniform: every
+// lane reads the same record and the words go to SGPRs, as the grouped form's ka.row[k] does from
+// the kernel arguments
+template <typename Row, typename Piece>
+__device__ __forceinline__ Row list_piece(const Piece *tbl, int i) {
+    constexpr int W = sizeof(Row) / 4;
+    static_assert(sizeof(Row) % 4 == 0, "a row record is whole 32-bit words");
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&tbl[i].r);
+    uint32_t w[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) w[j] = __builtin_amdgcn_readfirstlane(src[j]);
+    Row r;
+    __builtin_memcpy(&r, w, sizeof(Row));
+    return r;
+}
+
 }  // namespace wrnn

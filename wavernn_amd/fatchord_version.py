@@ -367,6 +367,55 @@ class WaveRNN(nn.Module):
         self.train()
         return outputs
 
+    def generate_list(self, mels: Sequence, save_paths: Optional[Sequence] = None, *, noise=None,
+                      seed: Optional[int] = None, row_offset: int = 0, lanes: Optional[int] = None,
+                      verbose: bool = False) -> List[np.ndarray]:
+        """generate(mels[i], None, False, …) for a list of utterances of ANY lengths (each (1, feat,
+        T_i), T_i ≥ 21; unbatched: no folds) in one call: the eight XCDs are eight lanes, each runs
+        a queue of utterances back to back inside the persistent launch (longest first, each to the
+        least loaded lane), so nothing waits for the longest member and no row runs past its own
+        end (C-ABI wrnn_generate_list).  → the list of float64 waveforms.
+
+        `generate_list(mels, seed=s, row_offset=r)[i]` equals `generate(mels[i], None, False, …,
+        seed=s, row_offset=r + i)` bit for bit, for every `lanes` (1..8, default min(8, len(mels));
+        for tests and experiments) and every WRNN_TERMS_MB: utterance i is Philox row row_offset + i
+        with its step counter at 0, and its conditioning (MelResNet, frame records, W·frames GEMM)
+        runs per utterance with the shapes of its single call.  `noise`: a sequence of per-utterance
+        [hop·T_i][11] draws, indexed by the utterance's own step.  Modes and dims without a list
+        kernel (anything but MoL rnn / fc 512 dense or rnn 896 block-sparse: the one-row XCD kernels) raise
+        NotImplementedError; bad arguments raise ValueError before anything is queued."""
+        self.eval()
+        start = time.time()
+        with torch.no_grad():
+            ms = self._mel_list(mels)
+            if noise is not None and len(noise) != len(ms):
+                raise ValueError("noise holds one [hop·T][11] array per utterance")
+            if lanes is not None and not 1 <= int(lanes) <= 8:
+                raise ValueError("lanes is 1..8 (one per XCD)")
+            if any(m.shape[2] < 21 for m in ms):   # before the MelResNet launches: nothing is queued
+                raise ValueError("every utterance needs at least 21 frames (the fade-out)")
+            if self.mode != 'MOL':
+                raise NotImplementedError("generate_list runs the one-row XCD MoL kernels: this model is not MoL")
+            loop = self.loop_handle()
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            dev = ms[0].device
+            nz = None if noise is None else [torch.as_tensor(z, dtype=torch.float32).to(dev).contiguous() for z in noise]
+            fr = [self.frames(m) for m in ms]   # one MelResNet launch per utterance, at its own shape
+            outs = loop.generate_list(self._upsample_spec(), [f[0] for f in fr], [f[1] for f in fr], lanes=lanes,
+                                      noise=nz, seed=seed, row_offset=row_offset)
+            outputs = [condition.postprocess(o[None], False, 0, False, self.n_classes, f[2],
+                                             20 * self.hop_length).cpu().numpy() for o, f in zip(outs, fr)]
+        self.last_gen_seconds = time.time() - start
+        if verbose:
+            longest = max(o.shape[0] for o in outs)
+            self.gen_display(longest - 1, longest, len(outs), start)
+        for i, output in enumerate(outputs):
+            if save_paths is not None and save_paths[i] is not None:
+                dsp.save_wav(output, save_paths[i], self.sample_rate)
+        self.train()
+        return outputs
+
     # --------------------------------------------------------------------- streaming
     def stream(self, n_streams: int = 1, total_frames: Optional[int] = None, *, noise=None,
                seed: Optional[int] = None, row_offset: int = 0) -> "WaveRNNStream":

@@ -311,6 +311,55 @@ class FatchordLoop:
             self.check(stream)
         return out, labels
 
+    def generate_list(self, spec, mels, auxs, lanes: Optional[int] = None, noise=None, seed: int = 0,
+                      row_offset: int = 0, stream=None, check: bool = True) -> list:
+        """Whole utterances of unequal length in one call (C-ABI wrnn_generate_list): mels[i]
+        [1][feat][T_i] and auxs[i] [1][4·aux][T_i] (its MelResNet output) fp32 on this GPU → the loop
+        samples of each, [hop·T_i] fp32 on the GPU, bit for bit what generate_frames(spec, mels[i],
+        auxs[i], row_offset=row_offset + i) gives.  The XCDs are `lanes` (1..8, default
+        min(8, len(mels))) lanes, each running a queue of utterances back to back inside the
+        persistent launch.  `noise`: per-utterance [hop·T_i][11] draws.  Refusals before anything is
+        queued raise ValueError (bad arguments) or NotImplementedError (modes / dims without a list
+        kernel) and leave the handle as it was."""
+        if getattr(self, "_padded", False):
+            raise NotImplementedError("lists need rnn / fc / aux dims that are multiples of 4")
+        U = len(mels)
+        if U < 1 or len(auxs) != U or (noise is not None and len(noise) != U):
+            raise ValueError("mels, auxs (and noise) must be non-empty sequences of one length")
+        for name, ts, C in (("mel", mels, self.feat_dims), ("aux", auxs, 4 * self.aux_dims)):
+            for t in ts:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                        and t.dim() == 3 and t.shape[0] == 1 and t.shape[1] == C):
+                    raise ValueError(f"every {name} must be a contiguous fp32 CUDA tensor [1][{C}][T]")
+        T = [int(m.shape[2]) for m in mels]
+        if any(a.shape[2] != t for a, t in zip(auxs, T)):
+            raise ValueError("an aux has another frame count than its mel")
+        steps, _ = zip(*[spec.shape(1, max(t, 1), 0, 0) for t in T])
+        if noise is not None:
+            for i, z in enumerate(noise):
+                if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()) or \
+                        tuple(z.shape) != (steps[i], self.noise_k):
+                    raise ValueError(f"noise[{i}] must be a contiguous fp32 CUDA tensor [{steps[i]}][{self.noise_k}]")
+        if lanes is None:
+            lanes = min(8, U)
+        dev = mels[0].device
+        outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in steps]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        vps = ctypes.c_void_p * U
+        rc = nat.lib().wrnn_generate_list(
+            self._h, ctypes.byref(spec.cfg), vps(*[m.data_ptr() for m in mels]), vps(*[a.data_ptr() for a in auxs]),
+            (ctypes.c_int * U)(*T), U, int(lanes), vps(*[z.data_ptr() for z in noise]) if noise is not None else None,
+            ctypes.c_uint64(seed & (2 ** 64 - 1)), row_offset, vps(*[o.data_ptr() for o in outs]), stream)
+        if rc == -6:   # WRNN_EUNSUPPORTED
+            raise NotImplementedError((nat.lib().wrnn_last_error(self._h) or b"").decode(errors="replace"))
+        if rc == -1:   # WRNN_EINVAL: nothing was queued
+            raise ValueError((nat.lib().wrnn_last_error(self._h) or b"").decode(errors="replace"))
+        nat.check(self._h, rc)
+        if check:
+            self.check(stream)
+        return outs
+
     def push_streams(self, pushes, stream=None, check: bool = True) -> list:
         """Advance several sessions of this loop in one call (C-ABI wrnn_stream_push_group): `pushes`
         is a sequence of (FatchordStream, mel or None, final), each member with its own frames and
@@ -406,6 +455,23 @@ def stream_plan(spec, frames_received: int, final: bool = False, total_frames: O
                                               -1 if total_frames is None else int(total_frames),
                                               ctypes.byref(steps), ctypes.byref(audio)))
     return steps.value, audio.value
+
+
+def list_plan(frames, lanes: Optional[int] = None) -> Tuple[list, list, list]:
+    """The lane schedule of a list call (C-ABI wrnn_list_plan, host only): (lane_of, pos_in_lane,
+    lane_frames) for utterances of `frames` frames on `lanes` lanes (default min(8, len(frames))):
+    longest first, each to the least loaded lane, ties to the lower index / lowest lane.
+    lane_frames[k] is lane k's timeline in frames (× hop: steps).  Raises WrnnError(WRNN_EINVAL)
+    for an empty list, lanes outside 1..8 or an utterance under 21 frames."""
+    frames = [int(f) for f in frames]
+    U = len(frames)
+    if lanes is None:
+        lanes = min(8, U)
+    n = max(U, 1)
+    lane_of, pos = (ctypes.c_int * n)(), (ctypes.c_int * n)()
+    steps = (ctypes.c_int64 * max(int(lanes), 8))()
+    nat.check_cond(nat.lib().wrnn_list_plan((ctypes.c_int * n)(*frames), U, int(lanes), lane_of, pos, steps))
+    return list(lane_of)[:U], list(pos)[:U], list(steps)[:lanes]
 
 
 def stream_lookahead(spec) -> int:
