@@ -315,8 +315,9 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
  * stores) and growing one frees and reallocates it, which waits for the device.  A session fed
  * pushes of at most the size of its first ones settles after a few pushes (the stores double);
  * a larger push later synchronises once more.
- * Kernel aborts surface through wrnn_check(h, stream); sets wrnn_info.last_path (5 or 6) and
- * leaves wrnn_elapsed_ms at the last wrnn_generate's launch.  Argument errors (WRNN_EINVAL:
+ * Kernel aborts surface through wrnn_check(h, stream); sets wrnn_info.last_path (5 or 6; a wide
+ * session, wrnn_stream_open_wide: 7) and leaves wrnn_elapsed_ms at the last wrnn_generate's launch
+ * (a wide session sets it to the loop share of the push).  Argument errors (WRNN_EINVAL:
  * counts against the rule above, cap, injected draws too short) are found before anything is
  * queued and leave the session unchanged; any failure after that point kills the session
  * (every later push returns WRNN_EINVAL: close it).
@@ -333,7 +334,8 @@ int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, doubl
  * arrived at different times, have different lengths and receive frames at different moments share
  * the GPU, each row on its own XCD over its own step window.
  *   sessions [count]  members: sessions of any U on the same handle (and so the same loop kernel),
- *                     their rows together <= 8, none listed twice, none NULL
+ *                     their rows together <= 8 (all of them wide sessions, wrnn_stream_open_wide:
+ *                     <= 128), none listed twice, none NULL
  *   mel      [count]  member i's [U_i][feat_dims][n_i] (device), or NULL where n_i = 0 (the array
  *                     itself may be NULL when every n_i = 0)
  *   n, final [count]  as wrnn_stream_push, per member: different totals, different frames received
@@ -363,6 +365,53 @@ int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, doubl
  * except where a member's workspace must grow, as wrnn_stream_push. */
 int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const float *const *mel, const int *n,
                            const int *final, double *const *wave, const int *cap, int *n_out, void *stream);
+
+/* ---- Wide sessions: up to 128 session rows per push (wide-group addition, same ABI) ---------
+ * wrnn_stream_open with the same arguments, but the session runs on the many-row XCD kernel (16
+ * rows per XCD, the weights as register-resident MFMA operands; wrnn_info.last_path 7) and U may be
+ * 1..128.  wrnn_stream_push, wrnn_stream_push_group, wrnn_stream_plan and wrnn_stream_close take it
+ * like any other session: the same emission rule and look-ahead, the same argument checks and
+ * atomic refusals, the same weight binding.  A group whose members are all wide may hold up to 128
+ * rows; a group that mixes wide and narrow members is refused ("runs another loop kernel than
+ * member 0"); narrow groups keep their limit of 8.  The members of a wide group share one upsample
+ * cascade (WRNN_EINVAL otherwise: one interpolation launch serves them all).
+ *
+ * What a wide session promises.  A member's audio does not depend on its company: every wide
+ * launch is the four-quad instantiation of the kernel, whatever the row count, in which the batch
+ * rows are independent MFMA columns — a row's bits depend neither on how many rows share the
+ * launch nor on the XCD and slot it sits in, so a member of a wide group is bit-identical to the
+ * same session pushed alone on the same schedule (a wide group of one).  Against the oracle it lies
+ * within the project's bound (2e-5 on whole utterances), and with Philox draws it equals
+ * wrnn_generate_frames(seed, row_offset) within 1e-5.
+ * What it does not promise.  Bit-equality with the same session opened narrow: the kernel differs
+ * (MFMA sums are associated differently from the one-row kernel's), both lie within the bound.
+ * And the members' conditioning (MelResNet, frame-term GEMMs) still runs once per member per push;
+ * callers whose utterances advance in lock step should open ONE wide session of U rows instead.
+ *
+ * A push cuts the members' runnable steps into rounds at the distinct step counts in ascending
+ * order (all rows of one launch run the same number of steps; members that are done drop out
+ * between rounds and the rest are compacted: launch row r on XCD r % 8, slot r / 8), and the
+ * WRNN_TERMS_MB budget cuts every round into launches of floor(budget / (rows * 4608) - 1) steps,
+ * rows = the rows with a step to run in this push.  The per-row recurrent state lives in the
+ * session, so a row may sit in another slot in every launch, and nothing the launches leave on the
+ * handle is relied on: one-shot calls (their own many-row launches included), narrow sessions and
+ * lists may run between pushes in stream order.  A wide push that queues a persistent launch sets
+ * wrnn_elapsed_ms to the device time of its loop share (terms interpolation, draws, hop-area resets
+ * and persistent launches of all its rounds): the rest of the push is the members' conditioning.
+ * WRNN_EUNSUPPORTED (message in wrnn_last_error(h)) unless the handle is MoL rnn / fc 512 with the
+ * many-row kernel co-resident at four quads per XCD (wrnn_info.xcdm_rows == 128), and as
+ * wrnn_stream_open where the cascade has no frame-rate form or wrnn_melresnet refuses the channels. */
+int wrnn_stream_open_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                          const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                          uint64_t seed, int64_t row_offset, wrnn_stream_t **out);
+
+/* The round plan of a wide push as a function (host only, stateless): `count` members with
+ * steps[i] >= 0 runnable steps and rows[i] >= 1 rows, at most steps_per_launch steps per launch →
+ * the number of persistent launches, and for launch j < cap its first launch-local step, its step
+ * count and its rows (the surviving members' rows in member order; launch row r sits on XCD r % 8,
+ * slot r / 8).  Negative WRNN_E* (message in wrnn_cond_last_error) on bad counts or more than 128 rows. */
+int wrnn_wide_plan(const int *steps, const int *rows, int count, int steps_per_launch, int *launch_first,
+                   int *launch_steps, int *launch_rows, int cap);
 
 /* The emission rule as a function (host only, stateless): the counts a session reports after
  * frames_received frames (`final`: they were the last), total_frames as given to open (−1: unknown).

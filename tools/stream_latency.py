@@ -24,7 +24,22 @@ Beside it, on N mels of 401 frames from tick 0: a lock-step U = N session (the w
 against a group of N U = 1 sessions (the grouped kernel), wall µs per step of a row.
 Every shape is warmed by one untimed session first (code objects, rocBLAS algorithm choice); each
 figure is the median of --reps fresh sessions (a session allocates its workspaces in its first
-pushes: that is part of what a caller waits for, and it is included).  One JSON line per row."""
+pushes: that is part of what a caller waits for, and it is included).  One JSON line per row.
+
+    python tools/stream_latency.py --wide 8 16 32 64 128 [--legs a b] [--reps 3]
+
+--wide N (up to 128; nothing else runs): the server with more than eight open sessions.  N
+single-utterance Philox sessions of 401 frames, all open from tick 0, every session pushing 8
+frames per tick (99.8 ms of audio at hop 275) — leg (a) with ceil(N / 8) narrow group pushes per
+tick, one after the other (entry points every revision with group pushes has, so the same leg
+runs on an older library as the baseline), leg (b) with ONE wide group push per tick
+(stream(wide=True): the many-row kernel, 16 rows per XCD).  Per leg: wall time per tick (call to
+device idle; median, 90th percentile, maximum over the ticks of a run, each the median over the
+runs), the device time between stream events recorded around the tick's call(s), for leg (b) its
+split into loop (wrnn_elapsed_ms: interpolation, draws, resets and persistent launches of the
+push) and conditioning (the rest: per-member mel window, MelResNet, frame-term GEMMs, post),
+persistent launches per tick, × real time, and whether the N sessions are sustained: a tick
+carries 8 · 275 / 22 050 s of audio, so they are when the tick's wall time stays below that."""
 import argparse
 import json
 import os
@@ -181,6 +196,77 @@ def independent(model, N, c, reps, dev, d):
     assert np.array_equal(audio[False], audio[True]), "the lock-step session and the group produced different audio"
 
 
+def _wide_ticks(model, mels, c, wide, dev):
+    """N U = 1 sessions over `mels`, all from tick 0, c frames per tick and an empty final push:
+    one wide group push per tick, or ceil(N / 8) narrow ones.  → (audio [N][samples], per tick:
+    wall ms, device ms, loop ms (wide; else None), persistent launches)."""
+    spec, loop = model._upsample_spec(), model.loop_handle()
+    N, T = len(mels), mels[0].shape[2]
+    kw = {"wide": True} if wide else {}
+    sess = [model.stream(1, T, seed=1000, row_offset=i, **kw) for i in range(N)]
+    out, ticks = [[] for _ in range(N)], []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    try:
+        f = 0
+        while not sess[0]._session.finished:
+            n = min(c, T - f)
+            ran = stream_plan(spec, f + n, n == 0, T)[0] > stream_plan(spec, f, False, T)[0]
+            pushes = [(s._session, m[:, :, f:f + n].contiguous() if n else None, n == 0) for s, m in zip(sess, mels)]
+            groups = [pushes] if wide else [pushes[i:i + 8] for i in range(0, N, 8)]
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            e0.record()
+            got = [w for g in groups for w in loop.push_streams(g, check=False)]
+            e1.record()
+            torch.cuda.synchronize(dev)
+            wall = (time.perf_counter() - t0) * 1e3
+            ticks.append((wall, e0.elapsed_time(e1), loop.elapsed_ms() if wide and ran else None, len(groups) * ran))
+            for i, w in enumerate(got):
+                out[i].append(w)
+            f += n
+        loop.check()
+    finally:
+        for s in sess:
+            s.close()
+    return np.concatenate([torch.cat(o, 1).cpu().numpy() for o in out], 0), ticks
+
+
+def wide_case(model, N, legs, reps, dev, d):
+    """--wide N (module docstring): one JSON line per leg."""
+    med = statistics.median
+    T, c = 401, 8
+    mels = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=10 + i))[None].to(dev) for i in range(N)]
+    audio_ms = c * d.hop_length / d.sample_rate * 1e3
+    audio = {}
+    for leg in legs:
+        wide = leg == "b"
+        _wide_ticks(model, mels, c, wide, dev)
+        runs = [_wide_ticks(model, mels, c, wide, dev) for _ in range(reps)]
+        audio[leg] = runs[0][0]
+        full = [[t for t in r[1] if t[3]][1:-1] for r in runs]   # ticks of 8 frames with a launch; not the first, not the flush
+
+        def stat(k, fn):
+            return round(med(fn([t[k] for t in ticks]) for ticks in full), 3)
+
+        def p90(v):
+            return sorted(v)[int(0.9 * (len(v) - 1))]
+
+        row = {"what": "wide: " + ("one wide group push per tick" if wide else "ceil(N / 8) narrow group pushes per tick"),
+               "leg": leg, "sessions": N, "frames": T, "chunk_frames": c, "audio_ms_per_tick": round(audio_ms, 2),
+               "ticks_measured": len(full[0]), "tick_wall_ms_median": stat(0, med), "tick_wall_ms_p90": stat(0, p90),
+               "tick_wall_ms_max": stat(0, max), "tick_device_ms_median": stat(1, med),
+               "launches_per_tick": full[0][0][3], "reps": reps}
+        if wide:
+            row["tick_loop_ms_median"] = stat(2, med)
+            row["tick_conditioning_ms_median"] = round(med(med(t[1] - t[2] for t in ticks) for ticks in full), 3)
+        row["x_real_time"] = round(N * audio_ms / row["tick_wall_ms_median"], 1)
+        row["sustained"] = bool(row["tick_wall_ms_p90"] < audio_ms)
+        print(json.dumps(row), flush=True)
+    if len(audio) == 2:
+        print(json.dumps({"what": "wide: leg (b) against leg (a), the same sessions on the two kernels", "sessions": N,
+                          "max_abs_diff": float(np.abs(audio["a"] - audio["b"]).max())}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--chunks", type=int, nargs="+", default=[4, 8, 32])
@@ -189,7 +275,13 @@ def main():
     ap.add_argument("--independent", type=int, default=8, metavar="N",
                     help="sessions of the server case (1..8; 0: skip it)")
     ap.add_argument("--only-independent", action="store_true", help="skip the single-session latency rows")
+    ap.add_argument("--wide", type=int, nargs="+", default=[], metavar="N",
+                    help="only the wide-group case, for each N (1..128) sessions")
+    ap.add_argument("--legs", nargs="+", choices=["a", "b"], default=["a", "b"],
+                    help="--wide: a = narrow group pushes (runs on older libraries too), b = one wide group push")
     args = ap.parse_args()
+    if any(not 1 <= n <= 128 for n in args.wide):
+        ap.error("--wide takes 1..128 sessions (a wide group has at most 128 rows)")
     if not 0 <= args.independent <= 8:
         ap.error("--independent takes 0..8 sessions (a group has at most 8 rows)")
     if not torch.cuda.is_available():
@@ -199,6 +291,11 @@ def main():
     model = WaveRNN(**d.ctor_kwargs()).to(dev)
     model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(d, 0).items()})
     model.eval()
+    if args.wide:
+        for n in args.wide:
+            wide_case(model, n, args.legs, args.reps, dev, d)
+        model.train()
+        return
     mel = torch.from_numpy(syn.make_mel(d.feat_dims, args.frames, seed=1))[None].to(dev)
     med = statistics.median
 

@@ -22,7 +22,7 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_frame_weights", "wrnn_melresnet_floats", "wrnn_melresnet", "wrnn_philox_draws",
            "wrnn_melresnet_tile_frames", "wrnn_stream_open", "wrnn_stream_push", "wrnn_stream_plan",
            "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint",
-           "wrnn_list_plan", "wrnn_generate_list")
+           "wrnn_list_plan", "wrnn_generate_list", "wrnn_stream_open_wide", "wrnn_wide_plan")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -113,6 +113,11 @@ def lib() -> ctypes.CDLL:
     L.wrnn_stream_open.argtypes = [vp, ctypes.POINTER(UpsampleCfg), ctypes.POINTER(MelResNetCfg), vp, i32, i32, vp, i32,
                                    u64, i64, ctypes.POINTER(vp)]
     L.wrnn_stream_open.restype = i32
+    L.wrnn_stream_open_wide.argtypes = L.wrnn_stream_open.argtypes
+    L.wrnn_stream_open_wide.restype = i32
+    # steps [count], rows [count], count, steps_per_launch → launch_first / launch_steps / launch_rows [cap], cap
+    L.wrnn_wide_plan.argtypes = [pi, pi, i32, i32, pi, pi, pi, i32]
+    L.wrnn_wide_plan.restype = i32
     L.wrnn_stream_push.argtypes = [vp, vp, i32, i32, vp, i32, pi, vp]
     L.wrnn_stream_push.restype = i32
     # arrays of `count` entries: sessions, mel pointers, n, final, wave pointers, cap, n_out

@@ -71,6 +71,11 @@ hipError_t prepare_xcdm_kernel(int max_lds_bytes);
 hipError_t xcdm_max_quads(int max_lds_bytes, bool raw, int *nq_max);
 hipError_t launch_philox_fill(float *out, unsigned long long seed, long long row0, int nb, int t0, int Lc, int K, int mol,
                               hipStream_t st);
+hipError_t launch_xcdm_group(const XcdmArgs &a, hipStream_t st);
+hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool *ok);
+hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, hipStream_t st);
+hipError_t launch_terms_interp_wide(const XcdmRow *rows, const float *coef, float *T, int N, int hop, int nJ, int nb,
+                                    int nt, hipStream_t st);
 hipError_t launch_dx(const DxArgs &a, hipStream_t st);
 hipError_t prepare_dx_kernel(int max_lds_bytes, bool *ok);
 int cond_fail(int code, const std::string &m);
@@ -201,6 +206,13 @@ struct wrnn_ctx {
     XcdPiece *d_ltab = nullptr, *h_ltab = nullptr;
     size_t ltab_cap = 0, hltab_cap = 0;             // records
     hipEvent_t ev_ltab = nullptr;
+    // wide streaming groups (wrnn_stream_open_wide): the many-row kernel's grouped instantiation is
+    // co-resident; the row tables of one push's launches (device, pinned staging copy, and the event
+    // that marks the end of the last upload, as for the list calls)
+    bool xcdmg_ok = false;
+    XcdmRow *d_wtab = nullptr, *h_wtab = nullptr;
+    size_t wtab_cap = 0, hwtab_cap = 0;             // records
+    hipEvent_t ev_wtab = nullptr;
 };
 
 namespace {
@@ -2236,6 +2248,7 @@ int wrnn_create(const wrnn_config *cfg, int device, wrnn_t **out) {
             HIP_TRY(h, prepare_xcdm_kernel(h->max_lds));
             HIP_TRY(h, xcdm_max_quads(h->max_lds, false, &h->xcdm_nq));
             h->xcdm_ok = h->xcdm_nq >= 1;
+            if (h->xcdm_nq >= kMQuadMax) HIP_TRY(h, prepare_xcdm_group_kernel(h->max_lds, &h->xcdmg_ok));
         }
     }
     // RAW 9-bit, rnn / fc 512: the many-row XCD-resident kernel with the softmax head (every row count)
@@ -2850,6 +2863,7 @@ struct wrnn_stream {
     wrnn_t *h = nullptr;
     int device = 0;
     LoopPath path = P_XCD;
+    bool wide = false;              // wrnn_stream_open_wide: the many-row kernel's grouped launches (path P_XCDM)
     int U = 0, T_known = -1;
     wrnn_upsample_cfg ucfg{};
     std::vector<float> taps[4];
@@ -2956,21 +2970,27 @@ void wrnn_stream_close(wrnn_stream_t *s) {
     delete s;
 }
 
-int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
-                     const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
-                     uint64_t seed, int64_t row_offset, wrnn_stream_t **out) {
+static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                       const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                       uint64_t seed, int64_t row_offset, wrnn_stream_t **out, bool wide) {
     if (!h) return WRNN_EINVAL;
     if (!out) return fail(h, WRNN_EINVAL, "need out");
     *out = nullptr;
     if (!h->ready) return fail(h, WRNN_ENOWEIGHTS, "weights not (fully) set");
     if (!ucfg || !mcfg || !melresnet_packed) return fail(h, WRNN_EINVAL, "need ucfg, mcfg and the packed MelResNet");
-    if (U < 1 || U > kXcds) return fail(h, WRNN_EINVAL, "a session has 1.." + std::to_string(kXcds) + " utterances");
+    const int U_max = wide ? kMRowsMax : kXcds;
+    if (U < 1 || U > U_max) return fail(h, WRNN_EINVAL, std::string(wide ? "a wide session" : "a session") + " has 1.." +
+                                                            std::to_string(U_max) + " utterances");
     if (total_frames < -1) return fail(h, WRNN_EINVAL, "total_frames is a frame count or -1");
     if (noise && noise_steps < 1) return fail(h, WRNN_EINVAL, "noise needs noise_steps >= 1");
     if (h->dm || h->cfg.mode != WRNN_MODE_MOL)
         return fail(h, WRNN_EUNSUPPORTED, "streaming sessions run the one-row XCD MoL kernels: this handle is not MoL");
-    const LoopPath path = choose_path(h, U);
-    if (path != P_XCD && path != P_XCDS)
+    if (wide && !(h->xcdm_ok && h->xcdmg_ok && h->xcdm_nq >= kMQuadMax))
+        return fail(h, WRNN_EUNSUPPORTED,
+                    "wide streaming sessions run the many-row XCD kernel with four co-resident quads per XCD (MoL, rnn / fc "
+                    "512, a full MI355X): this handle does not have it");
+    const LoopPath path = wide ? P_XCDM : choose_path(h, U);
+    if (!wide && path != P_XCD && path != P_XCDS)
         return fail(h, WRNN_EUNSUPPORTED,
                     "streaming sessions run the dense rnn/fc 512 XCD kernel or the block-sparse rnn 896 one; " +
                         std::to_string(U) + " row(s) of this handle take loop path " + std::to_string((int)path));
@@ -2987,6 +3007,7 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
     s->device = h->device;
     s->loads = h->loads;
     s->path = path;
+    s->wide = wide;
     s->U = U;
     s->T_known = total_frames;
     s->ucfg = *ucfg;
@@ -3012,24 +3033,43 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
     }
     const int tile = wrnn_melresnet_tile_frames(mcfg, U, 1);
     if (tile < 0) return fail(h, tile, "the MelResNet kernel does not cover these channel counts");
-    s->N = kXcdWgs * (path == P_XCD ? kXTerms : kSTerms);
-    s->state_w = path == P_XCD ? kXStateW : kSStateW;
+    // wide: the many-row kernel's compact record and one state record per row and workgroup; its
+    // launches restart their tags over the handle's hop area, so the session owns no granules
+    s->N = kXcdWgs * (wide ? kMRing : path == P_XCD ? kXTerms : kSTerms);
+    s->state_w = wide ? kMRowStateW : path == P_XCD ? kXStateW : kSStateW;
     s->FT.row = s->AT.row = (size_t)U * s->N;
     const size_t tail_n = (size_t)std::max(1, 2 * s->pad) * U * feat;
     HIP_TRY(h, hipMalloc(&s->d_coef, coef.size() * sizeof(float)));
     HIP_TRY(h, hipMalloc(&s->d_state, (size_t)U * kXcdWgs * s->state_w * sizeof(float)));
-    HIP_TRY(h, hipMalloc(&s->d_xg, (size_t)U * kXXcdStride * 8));
+    if (wide) {
+        if (!h->d_xmxg) HIP_TRY(h, hipMalloc(&h->d_xmxg, (size_t)kXcds * kMXcdStride * 8));
+        if (!h->ev_wtab) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_wtab, hipEventDisableTiming));
+    } else {
+        HIP_TRY(h, hipMalloc(&s->d_xg, (size_t)U * kXXcdStride * 8));
+    }
     for (int i = 0; i < 2; ++i) {
         HIP_TRY(h, hipMalloc(&s->d_tail[i], tail_n * sizeof(float)));
         HIP_TRY(h, hipMemset(s->d_tail[i], 0, tail_n * sizeof(float)));
     }
     HIP_TRY(h, hipMemcpy(s->d_coef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(s->d_xg, 0, (size_t)U * kXXcdStride * 8));   // hop tags are step + 1: they start at 1
+    if (s->d_xg) HIP_TRY(h, hipMemset(s->d_xg, 0, (size_t)U * kXXcdStride * 8));   // hop tags are step + 1: they start at 1
     HIP_TRY(h, hipMemset(s->d_state, 0, (size_t)U * kXcdWgs * s->state_w * sizeof(float)));
     if (!h->d_members) HIP_TRY(h, hipMalloc(&h->d_members, kXcds * sizeof(int)));
     HIP_TRY(h, hipDeviceSynchronize());   // the memsets are asynchronous to the host
     *out = s.release();
     return WRNN_OK;
+}
+
+int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                     const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                     uint64_t seed, int64_t row_offset, wrnn_stream_t **out) {
+    return stream_open(h, ucfg, mcfg, melresnet_packed, U, total_frames, noise, noise_steps, seed, row_offset, out, false);
+}
+
+int wrnn_stream_open_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                          const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                          uint64_t seed, int64_t row_offset, wrnn_stream_t **out) {
+    return stream_open(h, ucfg, mcfg, melresnet_packed, U, total_frames, noise, noise_steps, seed, row_offset, out, true);
 }
 
 // One persistent launch per time chunk of the steps [t_begin, t_end) of a push, through the kernel's
@@ -3139,8 +3179,20 @@ static int stream_prepare(wrnn_stream *s, StreamPush &p, hipStream_t st) {
     if (rocblas_set_stream(h->blas, st) != rocblas_status_success) return fail(h, WRNN_EHIP, "rocblas_set_stream failed");
     const float one = 1.0f, zero = 0.0f;
     // C[m][N] = W·X for `frames` frame records in d_frec, through the path's terms GEMM
+    XcdmGemm wgemms[3];
+    if (s->wide) xcdm_terms_gemms(*h, wgemms);
     auto gemm = [&](int frames, float ones, float *C) -> int {
         HIP_TRY(h, ensure(s->d_X, s->X_cap, (size_t)frames * U * KX));
+        if (s->wide) {   // the many-row kernel's three segmented GEMMs on the split input (generate_xcdm)
+            HIP_TRY(h, launch_pack_cond_input(s->d_frec, h->CD, U, 0, U, 0, frames, KX, s->d_X, st,
+                                              h->cfg.feat_dims + h->cfg.aux_dims, ones));
+            for (const XcdmGemm &g : wgemms)
+                if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, g.rows, frames * U, g.k, &one,
+                                  h->d_xmWt + (size_t)g.row0 * KX + g.col0, KX, s->d_X + g.col0, KX, &zero, C + g.row0,
+                                  N) != rocblas_status_success)
+                    return fail(h, WRNN_EHIP, "rocblas_sgemm (frame terms) failed");
+            return WRNN_OK;
+        }
         HIP_TRY(h, launch_pack_cond_input(s->d_frec, h->CD, U, 0, U, 0, frames, KX, s->d_X, st, 0, ones));
         if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, frames * U, KX, &one, h->d_xWt,
                           KX, s->d_X, KX, &zero, C, N) != rocblas_status_success)
@@ -3228,7 +3280,157 @@ static int stream_finish(wrnn_stream *s, const StreamPush &p, int *n_out, hipStr
     return WRNN_OK;
 }
 
-// The group of one, through the launch-wide windowed kernel
+// ---- wide groups: the members' rows through the many-row kernel's grouped instantiation ------------
+// The round plan of one push (host only): members with step counts n[i] (0: none) are cut into rounds
+// at the distinct counts in ascending order — round r runs launch-local steps [cut[r − 1], cut[r]) of
+// every member with n[i] ≥ cut[r] — and every round into launches of at most Lc_max steps.  The rows
+// of a launch are the surviving members' rows in member order, compacted: launch row r sits on XCD
+// r % 8, slot r / 8.  → (first step, steps, rows) per launch.
+struct WideLaunch {
+    int off, Lc, rows;
+};
+static std::vector<WideLaunch> wide_plan(const int *n, const int *U, int count, int Lc_max) {
+    std::vector<int> cuts;
+    for (int i = 0; i < count; ++i)
+        if (n[i] > 0) cuts.push_back(n[i]);
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    std::vector<WideLaunch> ls;
+    int prev = 0;
+    for (int c : cuts) {
+        int rows = 0;
+        for (int i = 0; i < count; ++i)
+            if (n[i] >= c) rows += U[i];
+        for (int off = prev; off < c; off += Lc_max) ls.push_back({off, std::min(Lc_max, c - off), rows});
+        prev = c;
+    }
+    return ls;
+}
+
+int wrnn_wide_plan(const int *steps, const int *rows, int count, int steps_per_launch, int *launch_first,
+                   int *launch_steps, int *launch_rows, int cap) {
+    if (!steps || !rows || count < 1 || steps_per_launch < 1) return cond_fail(WRNN_EINVAL, "need steps, rows, count >= 1 and steps_per_launch >= 1");
+    int total = 0;
+    for (int i = 0; i < count; ++i) {
+        if (steps[i] < 0 || rows[i] < 1) return cond_fail(WRNN_EINVAL, "a member has steps >= 0 and rows >= 1");
+        total += rows[i];
+    }
+    if (total > kMRowsMax) return cond_fail(WRNN_EINVAL, "a wide group has at most " + std::to_string(kMRowsMax) + " rows");
+    const std::vector<WideLaunch> ls = wide_plan(steps, rows, count, steps_per_launch);
+    for (size_t j = 0; j < ls.size() && (int)j < cap; ++j) {
+        if (launch_first) launch_first[j] = ls[j].off;
+        if (launch_steps) launch_steps[j] = ls[j].Lc;
+        if (launch_rows) launch_rows[j] = ls[j].rows;
+    }
+    return (int)ls.size();
+}
+
+// Per launch of the plan: the row table (uploaded once for the whole push), one interpolation launch
+// into the shared terms, one draws launch, the hop area reset to all-ones (tags and slot parities
+// restart at every launch), the membership counters, one persistent launch.  Nothing here outlives
+// the launch on the handle: the terms, the draws and the hop area are rewritten before each one, the
+// state lives in the sessions' records — so one-shot calls and narrow sessions may run in between.
+static int wide_group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPush *ps, int count, hipStream_t st) {
+    std::vector<int> n(count), U(count);
+    int rows = 0, longest = 0;
+    for (int i = 0; i < count; ++i) {
+        n[i] = (int)ps[i].S_new - ps[i].S_old;
+        U[i] = ss[i]->U;
+        if (n[i] > 0) {
+            rows += U[i];
+            longest = std::max(longest, n[i]);
+        }
+    }
+    if (rows == 0) return WRNN_OK;
+    const int N = kXcdWgs * kMRing;
+    const char *mb_env = std::getenv("WRNN_TERMS_MB");
+    const double budget = (mb_env ? std::atof(mb_env) : 8192.0) * (1 << 20) / 4.0;   // floats
+    const int Lc_max = (int)std::max(1.0, std::min((double)longest, budget / ((double)rows * N) - 1.0));
+    const std::vector<WideLaunch> ls = wide_plan(n.data(), U.data(), count, Lc_max);
+    size_t ntab = 0;
+    for (const WideLaunch &l : ls) ntab += (size_t)l.rows;
+    if (grow(h, h->d_T, h->T_cap, (size_t)(Lc_max + 1) * rows * N) ||
+        grow(h, h->d_xmnoise, h->xmnoise_cap, (size_t)Lc_max * rows * 11))
+        return WRNN_EHIP;
+    HIP_TRY(h, ensure(h->d_wtab, h->wtab_cap, ntab));
+    if (!h->d_members) HIP_TRY(h, hipMalloc(&h->d_members, kXcds * sizeof(int)));
+    HIP_TRY(h, hipEventSynchronize(h->ev_wtab));   // the last push's upload has read the staging copy
+    if (ntab > h->hwtab_cap) {
+        if (h->h_wtab) HIP_TRY(h, hipHostFree(h->h_wtab));
+        h->h_wtab = nullptr;
+        h->hwtab_cap = 0;
+        HIP_TRY(h, hipHostMalloc((void **)&h->h_wtab, 2 * ntab * sizeof(XcdmRow), hipHostMallocDefault));
+        h->hwtab_cap = 2 * ntab;
+    }
+    size_t at = 0;
+    for (const WideLaunch &l : ls) {
+        for (int i = 0; i < count; ++i) {
+            if (n[i] <= l.off) continue;   // done (or without a step in this push): the member takes no slot
+            wrnn_stream *s = ss[i];
+            const int t0 = ps[i].S_old + l.off;
+            for (int u = 0; u < s->U; ++u) {
+                XcdmRow r{};
+                r.ft = s->FT.buf[s->FT.cur] + (size_t)u * N;
+                r.at = s->AT.buf[s->AT.cur] + (size_t)u * N;
+                r.fr_ld = (long long)s->U * N;
+                r.noise = s->noise ? s->noise + ((size_t)t0 * s->U + u) * 11 : nullptr;
+                r.noise_ld = (long long)s->U * 11;
+                r.seed = s->seed;
+                r.prow = s->row_offset + u;
+                r.out = s->d_y[s->y_cur] + (size_t)u * s->y_ld[s->y_cur] + (t0 - s->y_t0);
+                r.state = s->d_state + (size_t)u * kXcdWgs * kMRowStateW;
+                r.ft_base = (int)s->FT.base;
+                r.at_base = (int)s->AT.base;
+                r.t0 = t0;
+                r.resume = t0 > 0;
+                h->h_wtab[at++] = r;
+            }
+        }
+    }
+    if (at != ntab) return fail(h, WRNN_EINVAL, "wide group: the row tables do not match the plan");
+    // ---- queuing begins
+    HIP_TRY(h, hipMemcpyAsync(h->d_wtab, h->h_wtab, ntab * sizeof(XcdmRow), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipEventRecord(h->ev_wtab, st));
+    HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
+    h->last_path = (int)P_XCDM;
+    // wrnn_elapsed_ms: the loop share of this push (interpolation, draws, resets and persistent
+    // launches of all its rounds), so a caller can split a tick into conditioning and loop
+    HIP_TRY(h, hipEventRecord(h->ev0, st));
+    const wrnn_stream *s0 = ss[0];
+    at = 0;
+    for (const WideLaunch &l : ls) {
+        const XcdmRow *tab = h->d_wtab + at;
+        at += (size_t)l.rows;
+        HIP_TRY(h, launch_terms_interp_wide(tab, s0->d_coef, h->d_T, N, s0->hop, s0->nJ, l.rows, l.Lc, st));
+        HIP_TRY(h, launch_draws_wide(h->d_xmnoise, tab, l.rows, l.Lc, st));
+        // every packed hop element empty, every tag one no step carries (fatchord_xcdm.h)
+        HIP_TRY(h, hipMemsetAsync(h->d_xmxg, 0xFF, (size_t)kXcds * kMXcdStride * 8, st));
+        HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
+        XcdmArgs a{};
+        a.slab = h->d_xmslab;
+        a.terms = h->d_T;
+        a.noise = h->d_xmnoise;
+        a.nz_ts = l.rows;
+        a.nz_t0 = 0;
+        a.nz_b0 = 0;
+        a.xg = h->d_xmxg;
+        a.members = h->d_members;
+        a.ctl = h->d_ctl;
+        a.timeout_ticks = h->timeout_ticks;
+        a.t0 = 0;
+        a.Lc = l.Lc;
+        a.Bt = l.rows;
+        a.nb = l.rows;
+        a.s = h->xms;
+        a.rows = tab;
+        HIP_TRY(h, launch_xcdm_group(a, st));
+    }
+    HIP_TRY(h, hipEventRecord(h->ev1, st));
+    h->timed = true;
+    return WRNN_OK;
+}
+
+// The group of one, through the launch-wide windowed kernel (wide sessions: the wide group of one)
 int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, double *wave, int cap, int *n_out,
                      void *stream) {
     if (!s || !s->h) return WRNN_EINVAL;
@@ -3243,7 +3445,8 @@ int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, doubl
         HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
         h->last_path = (int)s->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
         int rc;
-        if (s->path == P_XCD) rc = stream_launches<XcdArgs>(s, p.S_old, (int)p.S_new, p.final, h->xs, launch_xcd, st);
+        if (s->wide) rc = wide_group_launches(h, &s, &p, 1, st);
+        else if (s->path == P_XCD) rc = stream_launches<XcdArgs>(s, p.S_old, (int)p.S_new, p.final, h->xs, launch_xcd, st);
         else rc = stream_launches<XcdsArgs>(s, p.S_old, (int)p.S_new, p.final, h->xss, launch_xcds, st);
         if (rc) return rc;
     }
@@ -3342,7 +3545,22 @@ int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const floa
             return fail(h, WRNN_EINVAL, "member " + std::to_string(i) + " runs another loop kernel than member 0");
         rows += sessions[i]->U;
     }
-    if (rows > kXcds)
+    const bool wide = sessions[0]->wide;
+    if (wide) {
+        if (rows > kMRowsMax)
+            return fail(h, WRNN_EINVAL, "a wide group has at most " + std::to_string(kMRowsMax) + " rows (" +
+                                            std::to_string(kMRowsXcd) + " per XCD): these members have " + std::to_string(rows));
+        // one interpolation launch serves every member: they share one upsample cascade
+        for (int i = 1; i < count; ++i) {
+            const wrnn_stream *a = sessions[0], *b = sessions[i];
+            bool same = a->hop == b->hop && a->nJ == b->nJ && a->jlo == b->jlo && a->pad == b->pad &&
+                        a->ucfg.n_scales == b->ucfg.n_scales;
+            for (int j = 0; same && j < a->ucfg.n_scales; ++j) same = a->taps[j] == b->taps[j];
+            if (!same)
+                return fail(h, WRNN_EINVAL, "member " + std::to_string(i) + " has another upsample cascade than member 0");
+        }
+    }
+    if (!wide && rows > kXcds)
         return fail(h, WRNN_EINVAL, "a group has at most " + std::to_string(kXcds) + " rows (one per XCD): these members have " +
                                         std::to_string(rows));
     std::vector<StreamPush> ps(count);
@@ -3361,7 +3579,8 @@ int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const floa
     for (int i = 0; i < count; ++i)
         if (int rc = stream_prepare(sessions[i], ps[i], st)) return rc;
     int rc;
-    if (sessions[0]->path == P_XCD) rc = group_launches<XcdGroupArgs>(h, sessions, ps.data(), count, h->xs, launch_xcd_group, st);
+    if (wide) rc = wide_group_launches(h, sessions, ps.data(), count, st);
+    else if (sessions[0]->path == P_XCD) rc = group_launches<XcdGroupArgs>(h, sessions, ps.data(), count, h->xs, launch_xcd_group, st);
     else rc = group_launches<XcdsGroupArgs>(h, sessions, ps.data(), count, h->xss, launch_xcds_group, st);
     if (rc) return rc;
     for (int i = 0; i < count; ++i)
@@ -3474,10 +3693,13 @@ void wrnn_destroy(wrnn_t *h) {
                     (void *)h->d_xmWt, (void *)h->d_coef, (void *)h->d_FT, (void *)h->d_AT, (void *)h->d_frec,
                     (void *)h->d_cond,
                     (void *)h->d_dxslab, (void *)h->d_dxstate, (void *)h->d_dxnoise, (void *)h->d_dxxg,
-                    (void *)h->d_larena, (void *)h->d_lstate, (void *)h->d_lxg, (void *)h->d_ltab})
+                    (void *)h->d_larena, (void *)h->d_lstate, (void *)h->d_lxg, (void *)h->d_ltab,
+                    (void *)h->d_wtab})
         if (p) (void)hipFree(p);
     if (h->h_ltab) (void)hipHostFree(h->h_ltab);
     if (h->ev_ltab) (void)hipEventDestroy(h->ev_ltab);
+    if (h->h_wtab) (void)hipHostFree(h->h_wtab);
+    if (h->ev_wtab) (void)hipEventDestroy(h->ev_wtab);
     if (h->blas) (void)rocblas_destroy_handle(h->blas);
     delete h;
 }

@@ -120,6 +120,32 @@ struct XcdmArgs {
     int L, t0, Lc, Bt, b0, nb;    // launch rows b0 .. b0 + nb - 1 of the call's Bt; nb <= kMRowsMax
     XcdmSlab s;
     unsigned *dbg;                // WRNN_DEBUG_STAMPS: [256 wg][kMWaves][kMDbgSteps][kMStamps] s_memtime, or nullptr
+    const struct XcdmRow *rows;   // grouped launches (kGrp): [nb] per-row records in device memory, else nullptr
+};
+
+// ---- grouped launches (wide streaming sessions, capi.cpp: wide_group_launches) -----------------
+// Launch row r (XCD r % 8, slot r / 8) belongs to some session at some step of its own.  The kernel
+// runs launch-local steps j = 0 .. Lc − 1 (t0 = 0: tags, slot parities and ring parities restart in
+// every launch, over a hop area the host has reset to all-ones); the row's absolute step appears
+// only in the bases below, which the host has already offset to the row's window.  The terms and
+// the draws of the launch are in the launch-shared layouts ([Lc][nb][N], [Lc][nb][11]) that the
+// table-driven kernels (terms_interp_wide_kernel, draws_wide_kernel) fill from the same records.
+// Per-row state, owned by the session: for each workgroup c one record of kMRowStateW floats —
+// h1 [16 own units], h2 [16], Σ W_hh1·h1 [3][16], Σ W_hh2·h2 [3][16], x (padded to 4) — so a row
+// may sit in another slot, or on another XCD, in every launch.
+constexpr int kMRowStateW = 16 + 16 + 48 + 48 + 4;
+struct XcdmRow {
+    const float *ft, *at;         // the row's frame-term stores (column u·N of its session's): row 0 = absolute row ft_base / at_base
+    long long fr_ld;              // floats between frame rows (U_s · N)
+    const float *noise;           // injected draws of the row's first step of this launch, or nullptr (Philox)
+    long long noise_ld;           // floats between steps (U_s · 11)
+    unsigned long long seed;      // Philox key: (seed, prow, absolute step)
+    long long prow;
+    float *out;                   // sample j of the launch at out[j]
+    float *state;                 // [kXcdWgs][kMRowStateW]
+    int ft_base, at_base;
+    int t0;                       // the row's absolute step at j = 0
+    int resume;                   // 0: the row starts from zero state (its step 0)
 };
 constexpr int kMStamps = 24, kMDbgSteps = 48, kMDbgSkip = 16;
 

@@ -33,6 +33,9 @@
 // The conditioning terms of step t + 1 (terms GEMM, capi.cpp) and its sampler noise are loaded
 // by waves 4..7 after their f1 poll and stored into an LDS ring before the step's last barrier.
 //
+// Wide streaming sessions (capi.cpp: wide_group_launches) run the grouped instantiation (kGrp;
+// fatchord_xcdm.h: XcdmRow): launch-local steps, per-row draws / output / state from a row table.
+//
 // Membership as in fatchord_xcd.hip (XCC id + per-XCD arrival counter; bounded waits).  fp32,
 // sums re-associated (MoL tolerance-checked against the oracle like the other kernels).
 #include <hip/hip_runtime.h>
@@ -552,7 +555,11 @@ __device__ __forceinline__ int rsample(const unsigned long long *lg, int n, uint
 // kRaw: the RAW (9-bit softmax) head — f2 published as a hop vector, fc3 (own 16 classes, A
 // operands in LDS) on the gathered f2 slice, the logits a sixth hop, rsample instead of msample;
 // the Exp(1) draws always come from `noise` (Philox pre-filled by the host).
-template <int NQ, bool kDbg, bool kRaw>
+// kGrp: the grouped launch of the wide streaming sessions (fatchord_xcdm.h: XcdmRow; NQ = 4, MoL,
+// no stamps): t0 = 0, so every step index below is launch-local; the state records and the output
+// base are the rows' own (a.rows), the terms and the draws the launch-shared arrays.  The step body
+// differs from the plain instantiation's only in the address of the sample store.
+template <int NQ, bool kDbg, bool kRaw, bool kGrp = false>
 __global__ __launch_bounds__(kMThreads, 1) void fatchord_xcdm_kernel(XcdmArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NR = 4 * NQ;
@@ -639,9 +646,32 @@ __global__ __launch_bounds__(kMThreads, 1) void fatchord_xcdm_kernel(XcdmArgs a)
     for (int i = tid; i < 3 * 16 * NR; i += kMThreads) gh1[i] = gh2[i] = 0.0f;
     if (tid < 16) xs[tid] = 0.0f;
     __syncthreads();
-    const bool resume = a.t0 > 0;
-    float *st = a.state + ((size_t)k * kXcdWgs + c) * kMStateW;
     float h1v = 0.0f, h2v = 0.0f;   // h1 / h2 of (unit gu, row gn): this thread's recurrent state
+    float *out_c = nullptr;         // kGrp: the output base of the row this workgroup samples (row c)
+    if constexpr (kGrp) {
+        // every thread is an epilogue thread (NQ = 4): (unit gu, slot gn) takes the record of
+        // launch row k + 8·gn, workgroup c, if that row exists and has run a step before
+        const bool live = gn < RX;
+        const XcdmRow *rw = a.rows + (k + kXcds * (live ? gn : 0));
+        if (live && rw->resume) {
+            const float *sr = rw->state + (size_t)c * kMRowStateW;
+            h1v = sr[gu];
+            h2v = sr[16 + gu];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                gh1[(q * 16 + gu) * NR + gn] = sr[32 + q * 16 + gu];
+                gh2[(q * 16 + gu) * NR + gn] = sr[80 + q * 16 + gu];
+            }
+            if (gu == 0) xs[gn] = sr[128];
+        }
+        if (c < RX) {
+            const unsigned long long ob = reinterpret_cast<unsigned long long>(a.rows[k + kXcds * c].out);
+            out_c = reinterpret_cast<float *>(((unsigned long long)__builtin_amdgcn_readfirstlane((int)(ob >> 32)) << 32) |
+                                              (unsigned)__builtin_amdgcn_readfirstlane((int)ob));
+        }
+    }
+    const bool resume = !kGrp && a.t0 > 0;
+    float *st = kGrp ? nullptr : a.state + ((size_t)k * kXcdWgs + c) * kMStateW;
     if (resume) {
         if (gru) {
             h1v = st[gu * 16 + gn];
@@ -999,7 +1029,8 @@ __global__ __launch_bounds__(kMThreads, 1) void fatchord_xcdm_kernel(XcdmArgs a)
                 const float xn = sample_row(c);
                 if (lane == 0) {
                     xpub(xg + kMHopOff[MH_X] + c, tag, xn);
-                    a.out[(size_t)(a.b0 + k + kXcds * c) * a.L + t] = xn;
+                    if constexpr (kGrp) out_c[t] = xn;
+                    else a.out[(size_t)(a.b0 + k + kXcds * c) * a.L + t] = xn;
                 }
             }
             // every workgroup: the x of all rows (lane n < RX polls row n)
@@ -1039,6 +1070,20 @@ __global__ __launch_bounds__(kMThreads, 1) void fatchord_xcdm_kernel(XcdmArgs a)
         }
     }
     // ---- carry the recurrent state to the next time chunk
+    if constexpr (kGrp) {
+        if (gn < RX) {
+            float *sr = a.rows[k + kXcds * gn].state + (size_t)c * kMRowStateW;
+            sr[gu] = h1v;
+            sr[16 + gu] = h2v;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                sr[32 + q * 16 + gu] = gh1[(q * 16 + gu) * NR + gn];
+                sr[80 + q * 16 + gu] = gh2[(q * 16 + gu) * NR + gn];
+            }
+            if (gu == 0) sr[128] = xs[gn];
+        }
+        return;
+    }
     if (gru) {
         st[gu * 16 + gn] = h1v;
         st[256 + gu * 16 + gn] = h2v;
@@ -1069,6 +1114,48 @@ hipError_t launch_philox_fill(float *out, unsigned long long seed, long long row
     hipLaunchKernelGGL(philox_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, seed, row0, nb, t0, Lc,
                        K, mol);
     return hipGetLastError();
+}
+
+// The draws of a grouped launch into the launch-shared layout [Lc][nb][11], from the row table:
+// row r's injected draws (its own pointer, already at its first step of the launch) or Philox keyed
+// by (the row's seed, its global row, its absolute step) — the key generate() gives that row.
+__global__ void draws_wide_kernel(float *out, const XcdmRow *rows, int nb, int Lc) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)Lc * nb * 11) return;
+    const int kk = (int)(i % 11), lr = (int)((i / 11) % nb), j = (int)(i / (11LL * nb));
+    const XcdmRow &r = rows[lr];
+    out[i] = r.noise ? r.noise[(size_t)j * r.noise_ld + kk]
+                     : philox_noise(r.seed, (unsigned long long)r.prow, (uint32_t)(r.t0 + j), (uint32_t)kk, 1);
+}
+
+hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, hipStream_t st) {
+    const long long n = (long long)Lc * nb * 11;
+    hipLaunchKernelGGL(draws_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, rows, nb, Lc);
+    return hipGetLastError();
+}
+
+// The grouped launch: always the four-quad instantiation, whatever the row count — batch rows are
+// independent MFMA columns there, so a row's bits depend neither on its company nor on its slot
+hipError_t launch_xcdm_group(const XcdmArgs &a, hipStream_t st) {
+    XcdmArgs args = a;
+    void *params[] = {&args};
+    return hipLaunchKernel((const void *)fatchord_xcdm_kernel<kMQuadMax, false, false, true>, dim3(kXcds * kXcdWgs),
+                           dim3(kMThreads), params, xcdm_lds_layout(kMQuadMax).total * sizeof(float), st);
+}
+
+// *ok: the grouped instantiation fits LDS and is co-resident (one workgroup per CU)
+hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool *ok) {
+    *ok = false;
+    const size_t lds = xcdm_lds_layout(kMQuadMax).total * sizeof(float);
+    if (lds > (size_t)max_lds_bytes) return hipSuccess;
+    const void *kf = (const void *)fatchord_xcdm_kernel<kMQuadMax, false, false, true>;
+    hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
+    if (e != hipSuccess) return e;
+    int n = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kf, kMThreads, lds);
+    if (e != hipSuccess) return e;
+    *ok = n >= 1;
+    return hipSuccess;
 }
 
 // RAW kernels have no stamp variant (the stamp buffer does not fit LDS beside the fc3 operands)

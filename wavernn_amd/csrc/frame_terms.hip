@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "fatchord_xcd.h"
+#include "fatchord_xcdm.h"
 
 namespace wrnn {
 
@@ -185,6 +186,59 @@ hipError_t launch_terms_interp_win(const float *FT, int ft_base, const float *AT
     InterpWinArgs a{FT, AT, coef, T, N, U, hop, nJ, ft_base, at_base, U, t0, nt};
     const dim3 grid(U * ((nt + kInterpSteps - 1) / kInterpSteps), (N / 4 + kInterpThreads - 1) / kInterpThreads);
     hipLaunchKernelGGL(terms_interp_win_kernel, grid, dim3(kInterpThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---- wide streaming groups (capi.cpp: wide_group_launches): the windowed pass for every row of one
+// launch, from the row table (fatchord_xcdm.h: XcdmRow) — row k's frame-term stores, their bases and
+// its first step — into column k of the launch-shared record [nt][nb][N].  The stores are in the
+// many-row kernel's segmented record order already (the pass is elementwise); per sample the sum
+// runs in terms_interp_kernel's order.
+__global__ __launch_bounds__(kInterpThreads) void terms_interp_wide_kernel(const XcdmRow *rows, const float *coef,
+                                                                            float *T, int N, int hop, int nJ, int nb,
+                                                                            int nt) {
+    const int c4 = blockIdx.y * kInterpThreads + threadIdx.x;   // float4 column
+    if (4 * c4 >= N) return;
+    const int nblk = (nt + kInterpSteps - 1) / kInterpSteps;
+    const int k = blockIdx.x / nblk, tb = (blockIdx.x - k * nblk) * kInterpSteps;
+    const XcdmRow &r = rows[k];
+    const size_t rs = (size_t)r.fr_ld;                          // frame-row stride
+    const float *A0 = r.at + 4 * c4, *F0 = r.ft + 4 * c4;
+    float4 fr[kInterpMaxJ], ar = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int loaded = -1;
+    for (int i = 0; i < kInterpSteps; ++i) {
+        const int tl = tb + i;
+        if (tl >= nt) break;
+        const int p = r.t0 + tl;
+        const int f = p / hop;
+        if (f != loaded) {
+            ar = *reinterpret_cast<const float4 *>(A0 + (size_t)(f - r.at_base) * rs);
+#pragma unroll
+            for (int j = 0; j < kInterpMaxJ; ++j)
+                if (j < nJ) fr[j] = *reinterpret_cast<const float4 *>(F0 + (size_t)(f + j - r.ft_base) * rs);
+            loaded = f;
+        }
+        float4 acc = ar;
+        const float *cf = coef + (size_t)(p - f * hop) * nJ;
+#pragma unroll
+        for (int j = 0; j < kInterpMaxJ; ++j) {
+            if (j < nJ) {
+                const float w = cf[j];
+                acc.x = fmaf(w, fr[j].x, acc.x);
+                acc.y = fmaf(w, fr[j].y, acc.y);
+                acc.z = fmaf(w, fr[j].z, acc.z);
+                acc.w = fmaf(w, fr[j].w, acc.w);
+            }
+        }
+        *reinterpret_cast<float4 *>(T + ((size_t)tl * nb + k) * N + 4 * c4) = acc;
+    }
+}
+
+// Every row's stores hold the FT / AT rows of its steps [t0, t0 + nt); N % 4 == 0, nJ <= kInterpMaxJ
+hipError_t launch_terms_interp_wide(const XcdmRow *rows, const float *coef, float *T, int N, int hop, int nJ, int nb,
+                                    int nt, hipStream_t st) {
+    const dim3 grid(nb * ((nt + kInterpSteps - 1) / kInterpSteps), (N / 4 + kInterpThreads - 1) / kInterpThreads);
+    hipLaunchKernelGGL(terms_interp_wide_kernel, grid, dim3(kInterpThreads), 0, st, rows, coef, T, N, hop, nJ, nb, nt);
     return hipGetLastError();
 }
 

@@ -418,7 +418,7 @@ class WaveRNN(nn.Module):
 
     # --------------------------------------------------------------------- streaming
     def stream(self, n_streams: int = 1, total_frames: Optional[int] = None, *, noise=None,
-               seed: Optional[int] = None, row_offset: int = 0) -> "WaveRNNStream":
+               seed: Optional[int] = None, row_offset: int = 0, wide: bool = False) -> "WaveRNNStream":
         """A streaming session: push mel frames as the acoustic model produces them, get the audio
         that has become final — unbatched MoL generate() in pieces, the recurrent state kept on the
         GPU between pushes (C-ABI wrnn_stream_*).  `n_streams` utterances (1..8) advance in lock
@@ -432,8 +432,19 @@ class WaveRNN(nn.Module):
         open (by a generate() or a new stream() after load_state_dict, a training step or a `.data`
         update) its next push raises and the session is dead: close it and open a new one.  A
         change that only pushes would see (a `.data` update with no generate() or stream() after
-        it) is not detected: the session goes on with the weights it was opened with."""
-        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset)
+        it) is not detected: the session goes on with the weights it was opened with.
+
+        `wide=True` runs the session on the many-row kernel (16 rows per XCD; loop path 7):
+        `n_streams` may be 1..128, and push_streams takes up to 128 rows of wide sessions per call.
+        The emission rule, look-ahead, push() / finish() / close(), weight binding and refusals are
+        the same.  A wide member's audio does not depend on its company: every wide launch is the
+        kernel's four-quad form, in which batch rows are independent MFMA columns, so a member is
+        bit-identical alone, in any group, in any slot; it lies within the project's bound of the
+        oracle, and with `seed` equals generate(seed=, row_offset=) within MOL tolerance.  It is
+        NOT bit-identical to the same session opened narrow (another kernel, sums associated
+        differently), and the members' conditioning is not batched across sessions: callers who can
+        lock-step should open one U-wide session."""
+        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset, wide)
 
     def push_streams(self, pushes) -> list:
         """Advance several sessions of this model in one call: `pushes` is a sequence of
@@ -445,7 +456,9 @@ class WaveRNN(nn.Module):
         member gets its own frames and its own end, and all of them share one persistent launch per
         push, every row on its own XCD (C-ABI wrnn_stream_push_group), instead of one launch per
         session that leaves seven XCDs idle.  The members' rows together are at most 8; a finished
-        session is no longer listed.  Refusals raise ValueError and leave every member unchanged."""
+        session is no longer listed.  Refusals raise ValueError and leave every member unchanged.
+        A group whose members were all opened with wide=True may hold up to 128 rows (16 per XCD,
+        one persistent launch per round of equal step counts); wide and narrow members do not mix."""
         members = []
         for item in pushes:
             if not isinstance(item, (tuple, list)) or len(item) != 3 or not isinstance(item[0], WaveRNNStream):
@@ -460,10 +473,11 @@ class WaveRNN(nn.Module):
         return [w.cpu().numpy() for w in members[0][0].loop.push_streams(members)]
 
     def generate_stream(self, mels, chunk_frames: int = 8, *, noise=None, seed: Optional[int] = None,
-                        row_offset: int = 0):
+                        row_offset: int = 0, wide: bool = False):
         """generate(mels, None, False, ...) as a generator of float64 chunks, for a mel known up
         front: mels [1][feat][T] (or [U][feat][T], chunks [U][m]) pushed `chunk_frames` at a time
-        (or by the frame counts of a sequence).  The chunks concatenate to generate()'s output."""
+        (or by the frame counts of a sequence).  The chunks concatenate to generate()'s output.
+        `wide` is passed to stream(): up to 128 utterances in lock step on the many-row kernel."""
         device = next(self.parameters()).device
         mels = torch.as_tensor(mels, device=device).to(torch.float32)
         if mels.dim() != 3:
@@ -472,7 +486,7 @@ class WaveRNN(nn.Module):
         counts = [chunk_frames] * (-(-T // chunk_frames)) if isinstance(chunk_frames, int) else list(chunk_frames)
         if any(c < 1 for c in counts):
             raise ValueError("chunk_frames must be positive")
-        with self.stream(U, T, noise=noise, seed=seed, row_offset=row_offset) as s:
+        with self.stream(U, T, noise=noise, seed=seed, row_offset=row_offset, wide=wide) as s:
             f = 0
             for c in counts:
                 if f >= T:
@@ -584,7 +598,9 @@ class WaveRNNStream:
     WaveRNN.push_streams advances several sessions in one call, each at its own pace."""
 
     def __init__(self, model: WaveRNN, n_streams: int, total_frames: Optional[int], noise, seed: Optional[int],
-                 row_offset: int):
+                 row_offset: int, wide: bool = False):
+        if wide and not 1 <= int(n_streams) <= 128:
+            raise ValueError(f"a wide session has 1..128 utterances, not {n_streams!r}")
         device = next(model.parameters()).device
         if device.type != 'cuda':
             raise RuntimeError("WaveRNN.stream runs on the MI355X HIP path: move the model to a GPU "
@@ -598,7 +614,8 @@ class WaveRNNStream:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         cfg, packed = model._melresnet_packed()
         self._session = FatchordStream(model.loop_handle(), model._upsample_spec(), cfg, packed, n_streams,
-                                       total_frames, nz, seed, row_offset)
+                                       total_frames, nz, seed, row_offset, wide=wide)
+        self.wide = bool(wide)
         self.n_streams = n_streams
         self.lookahead_frames = self._session.lookahead_frames
 

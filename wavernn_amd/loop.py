@@ -365,8 +365,10 @@ class FatchordLoop:
         is a sequence of (FatchordStream, mel or None, final), each member with its own frames and
         its own end — what FatchordStream.push gives for each, bit for bit, but with one persistent
         launch per time chunk for all of them, every row on its own XCD.  The members' rows together
-        are at most 8.  → the new audio per member, float64 [U_i][m_i] on the GPU.  Refusals
-        (ValueError with the library's message) leave every member unchanged."""
+        are at most 8 — or, when every member is a wide session (FatchordStream(wide=True)), at
+        most 128, 16 per XCD on the many-row kernel; wide and narrow members do not mix.  → the new
+        audio per member, float64 [U_i][m_i] on the GPU.  Refusals (ValueError with the library's
+        message) leave every member unchanged."""
         members = []
         for item in pushes:
             if not isinstance(item, (tuple, list)) or len(item) != 3:
@@ -383,6 +385,11 @@ class FatchordLoop:
             members.append((s, mel, s._frames_of(mel), bool(final)))
         if not members:
             raise ValueError("push_streams needs at least one member")
+        if any(s.wide != members[0][0].wide for s, _, _, _ in members):
+            raise ValueError("a group holds wide sessions or narrow ones, not both: they run different loop kernels")
+        rows = sum(s.n_streams for s, _, _, _ in members)
+        if members[0][0].wide and rows > WIDE_ROWS:
+            raise ValueError(f"a wide group has at most {WIDE_ROWS} rows (16 per XCD): these members have {rows}")
         waves, plan = [], []
         for s, mel, n, final in members:
             try:
@@ -457,6 +464,36 @@ def stream_plan(spec, frames_received: int, final: bool = False, total_frames: O
     return steps.value, audio.value
 
 
+WIDE_ROWS = 128   # rows of a wide session or group: 16 per XCD (csrc/fatchord_xcdm.h: kMRowsMax)
+
+
+def wide_plan(steps, rows, steps_per_launch: int) -> list:
+    """The round plan of a wide group push (C-ABI wrnn_wide_plan, host only): members with
+    `steps[i]` runnable steps and `rows[i]` rows are cut into rounds at the distinct step counts in
+    ascending order, every round into launches of at most `steps_per_launch` steps → one
+    (first launch-local step, steps, [(member, utterance, xcd, slot) per launch row]) per persistent
+    launch: the surviving members' rows in member order, launch row r on XCD r % 8, slot r // 8.
+    Raises WrnnError(WRNN_EINVAL) on negative steps, rows < 1 or more than 128 rows."""
+    steps, rows = [int(x) for x in steps], [int(x) for x in rows]
+    if len(steps) != len(rows):
+        raise ValueError("steps and rows have one entry per member")
+    n = max(len(steps), 1)
+    ints = ctypes.c_int * n
+    args = (ints(*steps), ints(*rows), len(steps), int(steps_per_launch))
+    count = nat.lib().wrnn_wide_plan(*args, None, None, None, 0)
+    if count < 0:
+        nat.check_cond(count)
+    cap = max(count, 1)
+    first, ls, lr = (ctypes.c_int * cap)(), (ctypes.c_int * cap)(), (ctypes.c_int * cap)()
+    nat.check_cond(min(0, nat.lib().wrnn_wide_plan(*args, first, ls, lr, cap)))
+    plan = []
+    for j in range(count):
+        live = [(i, u) for i in range(len(steps)) if steps[i] > first[j] for u in range(rows[i])]
+        assert len(live) == lr[j], (j, len(live), lr[j])
+        plan.append((first[j], ls[j], [(i, u, r % 8, r // 8) for r, (i, u) in enumerate(live)]))
+    return plan
+
+
 def list_plan(frames, lanes: Optional[int] = None) -> Tuple[list, list, list]:
     """The lane schedule of a list call (C-ABI wrnn_list_plan, host only): (lane_of, pos_in_lane,
     lane_frames) for utterances of `frames` frames on `lanes` lanes (default min(8, len(frames))):
@@ -489,12 +526,21 @@ class FatchordStream:
     returned as soon as it is final.  The
     recurrent state, frame-term stores and mel tail live on the GPU in the session, so one-shot
     generate() calls and other sessions on the same loop may run between pushes.  Dims or modes
-    the session kernels do not cover raise NotImplementedError with the library's message."""
+    the session kernels do not cover raise NotImplementedError with the library's message.
+
+    `wide=True` opens the session on the many-row kernel (C-ABI wrnn_stream_open_wide, last_path
+    7): `n_streams` 1..128, and groups of wide sessions hold up to 128 rows.  A wide member's audio
+    is bit-identical whatever its company (every wide launch is the kernel's four-quad form, whose
+    batch rows are independent MFMA columns) and lies within the project's bound of the oracle; it
+    is NOT bit-identical to the same session opened narrow, which runs another kernel."""
 
     def __init__(self, loop: FatchordLoop, spec, mr_cfg, mr_packed: torch.Tensor, n_streams: int = 1,
                  total_frames: Optional[int] = None, noise: Optional[torch.Tensor] = None, seed: int = 0,
-                 row_offset: int = 0):
+                 row_offset: int = 0, wide: bool = False):
         self._s = None
+        self.wide = bool(wide)
+        if self.wide and not 1 <= int(n_streams) <= WIDE_ROWS:
+            raise ValueError(f"a wide session has 1..{WIDE_ROWS} utterances, not {n_streams!r}")
         if getattr(loop, "_padded", False):
             raise NotImplementedError("streaming sessions need rnn / fc / aux dims that are multiples of 4")
         if noise is not None:
@@ -510,7 +556,8 @@ class FatchordStream:
         self.lookahead_frames = stream_lookahead(spec)
         s = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            rc = nat.lib().wrnn_stream_open(loop._h, ctypes.byref(spec.cfg), ctypes.byref(mr_cfg), mr_packed.data_ptr(),
+            opener = nat.lib().wrnn_stream_open_wide if self.wide else nat.lib().wrnn_stream_open
+            rc = opener(loop._h, ctypes.byref(spec.cfg), ctypes.byref(mr_cfg), mr_packed.data_ptr(),
                                             n_streams, -1 if total_frames is None else int(total_frames),
                                             noise.data_ptr() if noise is not None else None,
                                             noise.shape[0] if noise is not None else 0,
