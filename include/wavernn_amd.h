@@ -400,10 +400,31 @@ int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const floa
  * and persistent launches of all its rounds): the rest of the push is the members' conditioning.
  * WRNN_EUNSUPPORTED (message in wrnn_last_error(h)) unless the handle is MoL rnn / fc 512 with the
  * many-row kernel co-resident at four quads per XCD (wrnn_info.xcdm_rows == 128), and as
- * wrnn_stream_open where the cascade has no frame-rate form or wrnn_melresnet refuses the channels. */
+ * wrnn_stream_open where the cascade has no frame-rate form or wrnn_melresnet refuses the channels.
+ *
+ * RAW handles.  A RAW handle (WRNN_MODE_RAW) opens wide sessions too — and only wide ones: the
+ * one-row kernels have no softmax head, wrnn_stream_open refuses it as before.  The session runs the
+ * grouped instantiation of the many-row kernel's RAW head under the same promises (every launch the
+ * four-quad form, a row's bits independent of company and slot); its class labels are those of
+ * wrnn_generate on the same draws, bit for bit, and a session returns audio only (a label is
+ * recovered from a sample x as (x + 1)·(n_classes − 1) / 2 when mu-law is off).
+ *   noise  [noise_steps][U][512] Exp(1) draws by absolute step, the layout wrnn_generate takes
+ *          for a RAW handle; NULL: Philox, the rows launch-for-launch those of wrnn_generate(seed,
+ *          row_offset + u)
+ * The draws of a RAW row-step (512 floats) share the WRNN_TERMS_MB budget with its terms: a round
+ * is cut into launches of floor(budget / (rows * (4608 + 512)) - 1) steps.
+ * WRNN_EUNSUPPORTED for a RAW handle names the condition that failed: n_classes != 512 (bits != 9),
+ * rnn / fc != 512, or no four-quad form of the many-row kernel on this device.  Deepmind handles
+ * are refused. */
 int wrnn_stream_open_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
                           const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
                           uint64_t seed, int64_t row_offset, wrnn_stream_t **out);
+
+/* RAW sessions: mu-law expansion of the emitted samples (RAW-session addition, same ABI).  on != 0:
+ * every sample v leaves as sign(v) / mu · ((1 + mu)^|v| − 1), mu = n_classes − 1, in float64, before
+ * the fade — wrnn_postprocess's mu_law.  The default is off.  Valid on a RAW session before its
+ * first push; WRNN_EINVAL on a MoL session or after a push, the session unchanged and usable. */
+int wrnn_stream_mu_law(wrnn_stream_t *s, int on);
 
 /* The round plan of a wide push as a function (host only, stateless): `count` members with
  * steps[i] >= 0 runnable steps and rows[i] >= 1 rows, at most steps_per_launch steps per launch →
@@ -412,6 +433,13 @@ int wrnn_stream_open_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_m
  * slot r / 8).  Negative WRNN_E* (message in wrnn_cond_last_error) on bad counts or more than 128 rows. */
 int wrnn_wide_plan(const int *steps, const int *rows, int count, int steps_per_launch, int *launch_first,
                    int *launch_steps, int *launch_rows, int cap);
+
+/* The steps per persistent launch a wide push takes (host only, stateless; reads WRNN_TERMS_MB as the
+ * push does): `rows` rows with a step to run, the longest member's runnable steps, raw != 0 for a RAW
+ * handle → min(longest_steps, floor(budget / (rows * 4608) - 1)) for MoL, floor(budget / (rows *
+ * (4608 + 512)) - 1) for RAW, at least 1: the steps_per_launch of wrnn_wide_plan.  Negative WRNN_E*
+ * (message in wrnn_cond_last_error) for rows outside 1..128 or longest_steps < 1. */
+int wrnn_wide_steps_per_launch(int rows, int longest_steps, int raw);
 
 /* The emission rule as a function (host only, stateless): the counts a session reports after
  * frames_received frames (`final`: they were the last), total_frames as given to open (−1: unknown).

@@ -26,7 +26,7 @@ Every shape is warmed by one untimed session first (code objects, rocBLAS algori
 figure is the median of --reps fresh sessions (a session allocates its workspaces in its first
 pushes: that is part of what a caller waits for, and it is included).  One JSON line per row.
 
-    python tools/stream_latency.py --wide 8 16 32 64 128 [--legs a b] [--reps 3]
+    python tools/stream_latency.py --wide 8 16 32 64 128 [--legs a b] [--reps 3] [--raw]
 
 --wide N (up to 128; nothing else runs): the server with more than eight open sessions.  N
 single-utterance Philox sessions of 401 frames, all open from tick 0, every session pushing 8
@@ -39,7 +39,10 @@ runs), the device time between stream events recorded around the tick's call(s),
 split into loop (wrnn_elapsed_ms: interpolation, draws, resets and persistent launches of the
 push) and conditioning (the rest: per-member mel window, MelResNet, frame-term GEMMs, post),
 persistent launches per tick, × real time, and whether the N sessions are sustained: a tick
-carries 8 · 275 / 22 050 s of audio, so they are when the tick's wall time stays below that."""
+carries 8 · 275 / 22 050 s of audio, so they are when the tick's wall time stays below that.
+--raw adds leg (r) in the same invocation: leg (b) on the RAW 9-bit rnn / fc 512 model (reference
+geometry, Philox, mu-law on) — the many-row kernel's softmax head, which adds the f2 and logits hops
+to every step — and the ratio of its loop share to leg (b)'s of the same run."""
 import argparse
 import json
 import os
@@ -231,17 +234,18 @@ def _wide_ticks(model, mels, c, wide, dev):
     return np.concatenate([torch.cat(o, 1).cpu().numpy() for o in out], 0), ticks
 
 
-def wide_case(model, N, legs, reps, dev, d):
-    """--wide N (module docstring): one JSON line per leg."""
+def wide_case(model, N, legs, reps, dev, d, raw_model=None):
+    """--wide N (module docstring): one JSON line per leg (raw_model: leg r after the others)."""
     med = statistics.median
     T, c = 401, 8
     mels = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=10 + i))[None].to(dev) for i in range(N)]
     audio_ms = c * d.hop_length / d.sample_rate * 1e3
-    audio = {}
-    for leg in legs:
-        wide = leg == "b"
-        _wide_ticks(model, mels, c, wide, dev)
-        runs = [_wide_ticks(model, mels, c, wide, dev) for _ in range(reps)]
+    audio, loop_ms = {}, {}
+    for leg in list(legs) + (["r"] if raw_model is not None else []):
+        wide = leg in ("b", "r")
+        mdl = raw_model if leg == "r" else model
+        _wide_ticks(mdl, mels, c, wide, dev)
+        runs = [_wide_ticks(mdl, mels, c, wide, dev) for _ in range(reps)]
         audio[leg] = runs[0][0]
         full = [[t for t in r[1] if t[3]][1:-1] for r in runs]   # ticks of 8 frames with a launch; not the first, not the flush
 
@@ -251,18 +255,22 @@ def wide_case(model, N, legs, reps, dev, d):
         def p90(v):
             return sorted(v)[int(0.9 * (len(v) - 1))]
 
-        row = {"what": "wide: " + ("one wide group push per tick" if wide else "ceil(N / 8) narrow group pushes per tick"),
+        row = {"what": "wide: " + ("RAW 9-bit, one wide group push per tick" if leg == "r" else
+                                   "one wide group push per tick" if wide else "ceil(N / 8) narrow group pushes per tick"),
                "leg": leg, "sessions": N, "frames": T, "chunk_frames": c, "audio_ms_per_tick": round(audio_ms, 2),
                "ticks_measured": len(full[0]), "tick_wall_ms_median": stat(0, med), "tick_wall_ms_p90": stat(0, p90),
                "tick_wall_ms_max": stat(0, max), "tick_device_ms_median": stat(1, med),
                "launches_per_tick": full[0][0][3], "reps": reps}
         if wide:
-            row["tick_loop_ms_median"] = stat(2, med)
+            row["tick_loop_ms_median"] = loop_ms[leg] = stat(2, med)
             row["tick_conditioning_ms_median"] = round(med(med(t[1] - t[2] for t in ticks) for ticks in full), 3)
         row["x_real_time"] = round(N * audio_ms / row["tick_wall_ms_median"], 1)
         row["sustained"] = bool(row["tick_wall_ms_p90"] < audio_ms)
         print(json.dumps(row), flush=True)
-    if len(audio) == 2:
+    if "b" in loop_ms and "r" in loop_ms:
+        print(json.dumps({"what": "wide: RAW loop share against the MoL wide leg of the same run", "sessions": N,
+                          "raw_over_mol_loop": round(loop_ms["r"] / loop_ms["b"], 3)}), flush=True)
+    if "a" in audio and "b" in audio:
         print(json.dumps({"what": "wide: leg (b) against leg (a), the same sessions on the two kernels", "sessions": N,
                           "max_abs_diff": float(np.abs(audio["a"] - audio["b"]).max())}), flush=True)
 
@@ -279,6 +287,8 @@ def main():
                     help="only the wide-group case, for each N (1..128) sessions")
     ap.add_argument("--legs", nargs="+", choices=["a", "b"], default=["a", "b"],
                     help="--wide: a = narrow group pushes (runs on older libraries too), b = one wide group push")
+    ap.add_argument("--raw", action="store_true",
+                    help="--wide: add leg r, the wide leg on the RAW 9-bit rnn / fc 512 model")
     args = ap.parse_args()
     if any(not 1 <= n <= 128 for n in args.wide):
         ap.error("--wide takes 1..128 sessions (a wide group has at most 128 rows)")
@@ -292,8 +302,14 @@ def main():
     model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(d, 0).items()})
     model.eval()
     if args.wide:
+        raw_model = None
+        if args.raw:
+            dr = syn.DEFAULT_RAW
+            raw_model = WaveRNN(**dr.ctor_kwargs()).to(dev)
+            raw_model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(dr, 0).items()})
+            raw_model.eval()
         for n in args.wide:
-            wide_case(model, n, args.legs, args.reps, dev, d)
+            wide_case(model, n, args.legs, args.reps, dev, d, raw_model)
         model.train()
         return
     mel = torch.from_numpy(syn.make_mel(d.feat_dims, args.frames, seed=1))[None].to(dev)

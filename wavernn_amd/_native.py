@@ -22,7 +22,8 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_frame_weights", "wrnn_melresnet_floats", "wrnn_melresnet", "wrnn_philox_draws",
            "wrnn_melresnet_tile_frames", "wrnn_stream_open", "wrnn_stream_push", "wrnn_stream_plan",
            "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint",
-           "wrnn_list_plan", "wrnn_generate_list", "wrnn_stream_open_wide", "wrnn_wide_plan")
+           "wrnn_list_plan", "wrnn_generate_list", "wrnn_stream_open_wide", "wrnn_wide_plan",
+           "wrnn_stream_mu_law", "wrnn_wide_steps_per_launch")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -33,6 +34,10 @@ class WrnnError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
         self.code = code
+
+
+class WrnnInvalid(WrnnError, ValueError):
+    """WRNN_EINVAL: an argument the library refused before it queued anything (also a ValueError)."""
 
 
 class Config(ctypes.Structure):
@@ -115,6 +120,10 @@ def lib() -> ctypes.CDLL:
     L.wrnn_stream_open.restype = i32
     L.wrnn_stream_open_wide.argtypes = L.wrnn_stream_open.argtypes
     L.wrnn_stream_open_wide.restype = i32
+    L.wrnn_stream_mu_law.argtypes = [vp, i32]
+    L.wrnn_stream_mu_law.restype = i32
+    L.wrnn_wide_steps_per_launch.argtypes = [i32, i32, i32]
+    L.wrnn_wide_steps_per_launch.restype = i32
     # steps [count], rows [count], count, steps_per_launch → launch_first / launch_steps / launch_rows [cap], cap
     L.wrnn_wide_plan.argtypes = [pi, pi, i32, i32, pi, pi, pi, i32]
     L.wrnn_wide_plan.restype = i32
@@ -153,4 +162,4 @@ def check_cond(code: int):
 def check(handle, code: int):
     if code != 0:
         msg = lib().wrnn_last_error(handle) if handle else b""
-        raise WrnnError(code, (msg or b"").decode(errors="replace"))
+        raise (WrnnInvalid if code == -1 else WrnnError)(code, (msg or b"").decode(errors="replace"))

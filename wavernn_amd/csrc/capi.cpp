@@ -71,9 +71,9 @@ hipError_t prepare_xcdm_kernel(int max_lds_bytes);
 hipError_t xcdm_max_quads(int max_lds_bytes, bool raw, int *nq_max);
 hipError_t launch_philox_fill(float *out, unsigned long long seed, long long row0, int nb, int t0, int Lc, int K, int mol,
                               hipStream_t st);
-hipError_t launch_xcdm_group(const XcdmArgs &a, hipStream_t st);
-hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool *ok);
-hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, hipStream_t st);
+hipError_t launch_xcdm_group(const XcdmArgs &a, bool raw, hipStream_t st);
+hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool raw, bool *ok);
+hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, int K, int mol, hipStream_t st);
 hipError_t launch_terms_interp_wide(const XcdmRow *rows, const float *coef, float *T, int N, int hop, int nJ, int nb,
                                     int nt, hipStream_t st);
 hipError_t launch_dx(const DxArgs &a, hipStream_t st);
@@ -85,7 +85,7 @@ hipError_t launch_terms_interp_win(const float *FT, int ft_base, const float *AT
 hipError_t launch_stream_mel_window(const float *tail_old, const float *chunk, int U, int feat, int n, int R_old,
                                     int keep, int w0, int wn, float *win, float *tail_new, hipStream_t st);
 hipError_t launch_postprocess_stream(const float *y, int U, int y_ld, int y_t0, int p0, int m, int wave_len,
-                                     int fade_len, double *wave, int cap, hipStream_t st);
+                                     int fade_len, int mu_law, double mu, double *wave, int cap, hipStream_t st);
 }  // namespace wrnn
 
 using namespace wrnn;
@@ -206,9 +206,9 @@ struct wrnn_ctx {
     XcdPiece *d_ltab = nullptr, *h_ltab = nullptr;
     size_t ltab_cap = 0, hltab_cap = 0;             // records
     hipEvent_t ev_ltab = nullptr;
-    // wide streaming groups (wrnn_stream_open_wide): the many-row kernel's grouped instantiation is
-    // co-resident; the row tables of one push's launches (device, pinned staging copy, and the event
-    // that marks the end of the last upload, as for the list calls)
+    // wide streaming groups (wrnn_stream_open_wide): the many-row kernel's grouped instantiation (of
+    // the handle's head, MoL or RAW) is co-resident; the row tables of one push's launches (device,
+    // pinned staging copy, and the event that marks the end of the last upload, as for the list calls)
     bool xcdmg_ok = false;
     XcdmRow *d_wtab = nullptr, *h_wtab = nullptr;
     size_t wtab_cap = 0, hwtab_cap = 0;             // records
@@ -2248,7 +2248,7 @@ int wrnn_create(const wrnn_config *cfg, int device, wrnn_t **out) {
             HIP_TRY(h, prepare_xcdm_kernel(h->max_lds));
             HIP_TRY(h, xcdm_max_quads(h->max_lds, false, &h->xcdm_nq));
             h->xcdm_ok = h->xcdm_nq >= 1;
-            if (h->xcdm_nq >= kMQuadMax) HIP_TRY(h, prepare_xcdm_group_kernel(h->max_lds, &h->xcdmg_ok));
+            if (h->xcdm_nq >= kMQuadMax) HIP_TRY(h, prepare_xcdm_group_kernel(h->max_lds, false, &h->xcdmg_ok));
         }
     }
     // RAW 9-bit, rnn / fc 512: the many-row XCD-resident kernel with the softmax head (every row count)
@@ -2258,6 +2258,7 @@ int wrnn_create(const wrnn_config *cfg, int device, wrnn_t **out) {
         HIP_TRY(h, prepare_xcdm_kernel(h->max_lds));
         HIP_TRY(h, xcdm_max_quads(h->max_lds, true, &h->xcdm_nq));
         h->xcdm_ok = h->xcdm_nq >= 1;
+        if (h->xcdm_nq >= kMQuadMax) HIP_TRY(h, prepare_xcdm_group_kernel(h->max_lds, true, &h->xcdmg_ok));
     }
     // MoL rnn 896 / fc 512: the XCD-resident block-sparse kernel, if the weights turn out
     // block-sparse (decided at wrnn_set_weights)
@@ -2864,6 +2865,9 @@ struct wrnn_stream {
     int device = 0;
     LoopPath path = P_XCD;
     bool wide = false;              // wrnn_stream_open_wide: the many-row kernel's grouped launches (path P_XCDM)
+    bool raw = false;               // a RAW handle's session (wide only): the softmax head, noise_k = kMRawNC Exp(1) draws
+    bool mu_law = false;            // RAW: wrnn_stream_mu_law — the emitted samples are mu-law expanded
+    int noise_k = 11;               // draws per row-step
     int U = 0, T_known = -1;
     wrnn_upsample_cfg ucfg{};
     std::vector<float> taps[4];
@@ -2983,8 +2987,26 @@ static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melr
                                                             std::to_string(U_max) + " utterances");
     if (total_frames < -1) return fail(h, WRNN_EINVAL, "total_frames is a frame count or -1");
     if (noise && noise_steps < 1) return fail(h, WRNN_EINVAL, "noise needs noise_steps >= 1");
-    if (h->dm || h->cfg.mode != WRNN_MODE_MOL)
+    const bool raw = !h->dm && h->cfg.mode == WRNN_MODE_RAW;
+    if (h->dm || (h->cfg.mode != WRNN_MODE_MOL && !(raw && wide)))
         return fail(h, WRNN_EUNSUPPORTED, "streaming sessions run the one-row XCD MoL kernels: this handle is not MoL");
+    if (raw) {   // the many-row kernel's softmax head: which of its conditions this handle misses
+        if (h->cfg.n_classes != kMRawNC)
+            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel's softmax head of " +
+                                                  std::to_string(kMRawNC) + " classes (bits = 9): this handle has " +
+                                                  std::to_string(h->cfg.n_classes) + " classes");
+        if (h->cfg.rnn_dims != 512 || h->cfg.fc_dims != 512)
+            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel (rnn / fc 512): this "
+                                              "handle has rnn " + std::to_string(h->cfg.rnn_dims) + ", fc " +
+                                                  std::to_string(h->cfg.fc_dims));
+        if (!(h->xcdm_ok && h->xcdm_nq >= kMQuadMax))
+            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel with four co-resident "
+                                              "quads per XCD (aux 32, a full MI355X): this handle does not have the "
+                                              "four-quad form");
+        if (!h->xcdmg_ok)
+            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel's grouped RAW "
+                                              "instantiation: it is not co-resident on this device");
+    }
     if (wide && !(h->xcdm_ok && h->xcdmg_ok && h->xcdm_nq >= kMQuadMax))
         return fail(h, WRNN_EUNSUPPORTED,
                     "wide streaming sessions run the many-row XCD kernel with four co-resident quads per XCD (MoL, rnn / fc "
@@ -3008,6 +3030,8 @@ static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melr
     s->loads = h->loads;
     s->path = path;
     s->wide = wide;
+    s->raw = raw;
+    s->noise_k = raw ? kMRawNC : 11;
     s->U = U;
     s->T_known = total_frames;
     s->ucfg = *ucfg;
@@ -3064,6 +3088,15 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
                      const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
                      uint64_t seed, int64_t row_offset, wrnn_stream_t **out) {
     return stream_open(h, ucfg, mcfg, melresnet_packed, U, total_frames, noise, noise_steps, seed, row_offset, out, false);
+}
+
+int wrnn_stream_mu_law(wrnn_stream_t *s, int on) {
+    if (!s || !s->h) return WRNN_EINVAL;
+    if (!s->raw) return fail(s->h, WRNN_EINVAL, "mu-law expansion belongs to RAW sessions: this session is MoL");
+    if (s->primed || s->fin || s->dead)
+        return fail(s->h, WRNN_EINVAL, "wrnn_stream_mu_law is set before the session's first push");
+    s->mu_law = on != 0;
+    return WRNN_OK;
 }
 
 int wrnn_stream_open_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
@@ -3268,7 +3301,8 @@ static int stream_finish(wrnn_stream *s, const StreamPush &p, int *n_out, hipStr
     if (p.m > 0) {
         const int T = p.final ? p.R_new : s->T_known;
         HIP_TRY(h, launch_postprocess_stream(s->d_y[s->y_cur], s->U, s->y_ld[s->y_cur], s->y_t0, s->audio, p.m,
-                                             T >= 0 ? (T - 1) * s->hop : -1, 20 * s->hop, p.wave, p.cap, st));
+                                             T >= 0 ? (T - 1) * s->hop : -1, 20 * s->hop, s->mu_law ? 1 : 0,
+                                             (double)(h->cfg.n_classes - 1), p.wave, p.cap, st));
     }
     s->R = p.R_new;
     s->A = p.A_new;
@@ -3307,6 +3341,23 @@ static std::vector<WideLaunch> wide_plan(const int *n, const int *U, int count, 
     return ls;
 }
 
+// Steps per persistent launch of a wide push: the WRNN_TERMS_MB budget over the floats of one step of
+// all rows with a step to run, one step kept back for the look-ahead row of the terms.  MoL: the
+// terms alone (the 11 uniforms are negligible beside them).  RAW: the terms and the kMRawNC draws.
+static int wide_steps_per_launch(int rows, int longest, bool raw) {
+    const int N = kXcdWgs * kMRing;
+    const char *mb_env = std::getenv("WRNN_TERMS_MB");
+    const double budget = (mb_env ? std::atof(mb_env) : 8192.0) * (1 << 20) / 4.0;   // floats
+    const double per_step = raw ? (double)rows * (N + kMRawNC) : (double)rows * N;
+    return (int)std::max(1.0, std::min((double)longest, budget / per_step - 1.0));
+}
+
+int wrnn_wide_steps_per_launch(int rows, int longest_steps, int raw) {
+    if (rows < 1 || rows > kMRowsMax || longest_steps < 1)
+        return cond_fail(WRNN_EINVAL, "need 1.." + std::to_string(kMRowsMax) + " rows and longest_steps >= 1");
+    return wide_steps_per_launch(rows, longest_steps, raw != 0);
+}
+
 int wrnn_wide_plan(const int *steps, const int *rows, int count, int steps_per_launch, int *launch_first,
                    int *launch_steps, int *launch_rows, int cap) {
     if (!steps || !rows || count < 1 || steps_per_launch < 1) return cond_fail(WRNN_EINVAL, "need steps, rows, count >= 1 and steps_per_launch >= 1");
@@ -3343,14 +3394,15 @@ static int wide_group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPu
     }
     if (rows == 0) return WRNN_OK;
     const int N = kXcdWgs * kMRing;
-    const char *mb_env = std::getenv("WRNN_TERMS_MB");
-    const double budget = (mb_env ? std::atof(mb_env) : 8192.0) * (1 << 20) / 4.0;   // floats
-    const int Lc_max = (int)std::max(1.0, std::min((double)longest, budget / ((double)rows * N) - 1.0));
+    // a handle has one mode: every member draws the same width (MoL: 11 uniforms; RAW: one Exp(1) per class)
+    const bool raw = ss[0]->raw;
+    const int K = ss[0]->noise_k;
+    const int Lc_max = wide_steps_per_launch(rows, longest, raw);
     const std::vector<WideLaunch> ls = wide_plan(n.data(), U.data(), count, Lc_max);
     size_t ntab = 0;
     for (const WideLaunch &l : ls) ntab += (size_t)l.rows;
     if (grow(h, h->d_T, h->T_cap, (size_t)(Lc_max + 1) * rows * N) ||
-        grow(h, h->d_xmnoise, h->xmnoise_cap, (size_t)Lc_max * rows * 11))
+        grow(h, h->d_xmnoise, h->xmnoise_cap, (size_t)Lc_max * rows * K))
         return WRNN_EHIP;
     HIP_TRY(h, ensure(h->d_wtab, h->wtab_cap, ntab));
     if (!h->d_members) HIP_TRY(h, hipMalloc(&h->d_members, kXcds * sizeof(int)));
@@ -3373,8 +3425,8 @@ static int wide_group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPu
                 r.ft = s->FT.buf[s->FT.cur] + (size_t)u * N;
                 r.at = s->AT.buf[s->AT.cur] + (size_t)u * N;
                 r.fr_ld = (long long)s->U * N;
-                r.noise = s->noise ? s->noise + ((size_t)t0 * s->U + u) * 11 : nullptr;
-                r.noise_ld = (long long)s->U * 11;
+                r.noise = s->noise ? s->noise + ((size_t)t0 * s->U + u) * K : nullptr;
+                r.noise_ld = (long long)s->U * K;
                 r.seed = s->seed;
                 r.prow = s->row_offset + u;
                 r.out = s->d_y[s->y_cur] + (size_t)u * s->y_ld[s->y_cur] + (t0 - s->y_t0);
@@ -3402,7 +3454,7 @@ static int wide_group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPu
         const XcdmRow *tab = h->d_wtab + at;
         at += (size_t)l.rows;
         HIP_TRY(h, launch_terms_interp_wide(tab, s0->d_coef, h->d_T, N, s0->hop, s0->nJ, l.rows, l.Lc, st));
-        HIP_TRY(h, launch_draws_wide(h->d_xmnoise, tab, l.rows, l.Lc, st));
+        HIP_TRY(h, launch_draws_wide(h->d_xmnoise, tab, l.rows, l.Lc, K, raw ? 0 : 1, st));
         // every packed hop element empty, every tag one no step carries (fatchord_xcdm.h)
         HIP_TRY(h, hipMemsetAsync(h->d_xmxg, 0xFF, (size_t)kXcds * kMXcdStride * 8, st));
         HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
@@ -3423,7 +3475,7 @@ static int wide_group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPu
         a.nb = l.rows;
         a.s = h->xms;
         a.rows = tab;
-        HIP_TRY(h, launch_xcdm_group(a, st));
+        HIP_TRY(h, launch_xcdm_group(a, raw, st));
     }
     HIP_TRY(h, hipEventRecord(h->ev1, st));
     h->timed = true;

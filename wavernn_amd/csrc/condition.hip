@@ -226,6 +226,8 @@ struct PostStreamArgs {
     double *wave;         // [U][cap]
     int U, y_ld, y_t0, p0, m, cap, wave_len, fade_len;
     double fout_step;
+    int mu_law;           // RAW sessions: expand (postprocess_kernel's mulaw) before the fade
+    double mu;            // n_classes − 1
 };
 
 __global__ void postprocess_stream_kernel(PostStreamArgs a) {
@@ -234,6 +236,11 @@ __global__ void postprocess_stream_kernel(PostStreamArgs a) {
     if (i >= a.m) return;
     const int p = a.p0 + i;
     double v = (double)a.y[(size_t)u * a.y_ld + (p - a.y_t0)];
+    if (a.mu_law) {
+        // np.sign(y) / mu * ((1 + mu) ** np.abs(y) - 1)   (utils/dsp.py:102)
+        const double sg = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
+        v = sg / a.mu * (pow(a.mu + 1.0, fabs(v)) - 1.0);
+    }
     if (a.wave_len >= 0) {
         const int q = p - (a.wave_len - a.fade_len);
         if (q >= 0) v = v * linspace_at(q, a.fade_len, 1.0, 0.0, a.fout_step);
@@ -242,10 +249,10 @@ __global__ void postprocess_stream_kernel(PostStreamArgs a) {
 }
 
 hipError_t launch_postprocess_stream(const float *y, int U, int y_ld, int y_t0, int p0, int m, int wave_len,
-                                     int fade_len, double *wave, int cap, hipStream_t st) {
+                                     int fade_len, int mu_law, double mu, double *wave, int cap, hipStream_t st) {
     if (m <= 0) return hipSuccess;
     PostStreamArgs a{y, wave, U, y_ld, y_t0, p0, m, cap, wave_len, fade_len,
-                     (0.0 - 1.0) / (double)(fade_len > 1 ? fade_len - 1 : 1)};
+                     (0.0 - 1.0) / (double)(fade_len > 1 ? fade_len - 1 : 1), mu_law, mu};
     hipLaunchKernelGGL(postprocess_stream_kernel, dim3((m + 255) / 256, U), dim3(256), 0, st, a);
     return hipGetLastError();
 }

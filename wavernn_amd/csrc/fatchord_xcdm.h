@@ -128,8 +128,12 @@ struct XcdmArgs {
 // runs launch-local steps j = 0 .. Lc − 1 (t0 = 0: tags, slot parities and ring parities restart in
 // every launch, over a hop area the host has reset to all-ones); the row's absolute step appears
 // only in the bases below, which the host has already offset to the row's window.  The terms and
-// the draws of the launch are in the launch-shared layouts ([Lc][nb][N], [Lc][nb][11]) that the
-// table-driven kernels (terms_interp_wide_kernel, draws_wide_kernel) fill from the same records.
+// the draws of the launch are in the launch-shared layouts ([Lc][nb][N], [Lc][nb][K]; K = 11 MoL
+// uniforms, or kMRawNC Exp(1) draws for the RAW head) that the table-driven kernels
+// (terms_interp_wide_kernel, draws_wide_kernel) fill from the same records.  The RAW head adds
+// nothing a session must own: its f2 vector and logits hop live in the hop area (reset with it, slot
+// n of an XCD = the launch row of this launch), its draws in the launch-shared array; labels are
+// not returned (a.labels = nullptr), the sample of a label is.
 // Per-row state, owned by the session: for each workgroup c one record of kMRowStateW floats —
 // h1 [16 own units], h2 [16], Σ W_hh1·h1 [3][16], Σ W_hh2·h2 [3][16], x (padded to 4) — so a row
 // may sit in another slot, or on another XCD, in every launch.
@@ -138,7 +142,7 @@ struct XcdmRow {
     const float *ft, *at;         // the row's frame-term stores (column u·N of its session's): row 0 = absolute row ft_base / at_base
     long long fr_ld;              // floats between frame rows (U_s · N)
     const float *noise;           // injected draws of the row's first step of this launch, or nullptr (Philox)
-    long long noise_ld;           // floats between steps (U_s · 11)
+    long long noise_ld;           // floats between steps (U_s · K: 11 MoL, kMRawNC RAW)
     unsigned long long seed;      // Philox key: (seed, prow, absolute step)
     long long prow;
     float *out;                   // sample j of the launch at out[j]

@@ -555,8 +555,8 @@ __device__ __forceinline__ int rsample(const unsigned long long *lg, int n, uint
 // kRaw: the RAW (9-bit softmax) head — f2 published as a hop vector, fc3 (own 16 classes, A
 // operands in LDS) on the gathered f2 slice, the logits a sixth hop, rsample instead of msample;
 // the Exp(1) draws always come from `noise` (Philox pre-filled by the host).
-// kGrp: the grouped launch of the wide streaming sessions (fatchord_xcdm.h: XcdmRow; NQ = 4, MoL,
-// no stamps): t0 = 0, so every step index below is launch-local; the state records and the output
+// kGrp: the grouped launch of the wide streaming sessions (fatchord_xcdm.h: XcdmRow; NQ = 4, MoL or
+// RAW head, no stamps): t0 = 0, so every step index below is launch-local; the state records and the output
 // base are the rows' own (a.rows), the terms and the draws the launch-shared arrays.  The step body
 // differs from the plain instantiation's only in the address of the sample store.
 template <int NQ, bool kDbg, bool kRaw, bool kGrp = false>
@@ -1116,39 +1116,47 @@ hipError_t launch_philox_fill(float *out, unsigned long long seed, long long row
     return hipGetLastError();
 }
 
-// The draws of a grouped launch into the launch-shared layout [Lc][nb][11], from the row table:
+// The draws of a grouped launch into the launch-shared layout [Lc][nb][K], from the row table:
 // row r's injected draws (its own pointer, already at its first step of the launch) or Philox keyed
 // by (the row's seed, its global row, its absolute step) — the key generate() gives that row.
-__global__ void draws_wide_kernel(float *out, const XcdmRow *rows, int nb, int Lc) {
+// K = 11, mol = 1: the MoL uniforms; K = kMRawNC, mol = 0: the Exp(1) draws of the RAW head (the
+// row launch_philox_fill(…, kMRawNC, 0) gives it in a one-shot call).
+__global__ void draws_wide_kernel(float *out, const XcdmRow *rows, int nb, int Lc, int K, int mol) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)Lc * nb * 11) return;
-    const int kk = (int)(i % 11), lr = (int)((i / 11) % nb), j = (int)(i / (11LL * nb));
+    if (i >= (long long)Lc * nb * K) return;
+    const int kk = (int)(i % K), lr = (int)((i / K) % nb), j = (int)(i / ((long long)K * nb));
     const XcdmRow &r = rows[lr];
     out[i] = r.noise ? r.noise[(size_t)j * r.noise_ld + kk]
-                     : philox_noise(r.seed, (unsigned long long)r.prow, (uint32_t)(r.t0 + j), (uint32_t)kk, 1);
+                     : philox_noise(r.seed, (unsigned long long)r.prow, (uint32_t)(r.t0 + j), (uint32_t)kk, mol);
 }
 
-hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, hipStream_t st) {
-    const long long n = (long long)Lc * nb * 11;
-    hipLaunchKernelGGL(draws_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, rows, nb, Lc);
+hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, int K, int mol, hipStream_t st) {
+    const long long n = (long long)Lc * nb * K;
+    hipLaunchKernelGGL(draws_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, rows, nb, Lc, K, mol);
     return hipGetLastError();
 }
 
 // The grouped launch: always the four-quad instantiation, whatever the row count — batch rows are
 // independent MFMA columns there, so a row's bits depend neither on its company nor on its slot
-hipError_t launch_xcdm_group(const XcdmArgs &a, hipStream_t st) {
-    XcdmArgs args = a;
-    void *params[] = {&args};
-    return hipLaunchKernel((const void *)fatchord_xcdm_kernel<kMQuadMax, false, false, true>, dim3(kXcds * kXcdWgs),
-                           dim3(kMThreads), params, xcdm_lds_layout(kMQuadMax).total * sizeof(float), st);
+// (raw: the softmax head's grouped instantiation, on its own LDS layout)
+static const void *xcdm_group_kernel(bool raw) {
+    return raw ? (const void *)fatchord_xcdm_kernel<kMQuadMax, false, true, true>
+               : (const void *)fatchord_xcdm_kernel<kMQuadMax, false, false, true>;
 }
 
-// *ok: the grouped instantiation fits LDS and is co-resident (one workgroup per CU)
-hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool *ok) {
+hipError_t launch_xcdm_group(const XcdmArgs &a, bool raw, hipStream_t st) {
+    XcdmArgs args = a;
+    void *params[] = {&args};
+    return hipLaunchKernel(xcdm_group_kernel(raw), dim3(kXcds * kXcdWgs), dim3(kMThreads), params,
+                           xcdm_lds_layout(kMQuadMax, false, raw).total * sizeof(float), st);
+}
+
+// *ok: the grouped instantiation (MoL or RAW head) fits LDS and is co-resident (one workgroup per CU)
+hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool raw, bool *ok) {
     *ok = false;
-    const size_t lds = xcdm_lds_layout(kMQuadMax).total * sizeof(float);
+    const size_t lds = xcdm_lds_layout(kMQuadMax, false, raw).total * sizeof(float);
     if (lds > (size_t)max_lds_bytes) return hipSuccess;
-    const void *kf = (const void *)fatchord_xcdm_kernel<kMQuadMax, false, false, true>;
+    const void *kf = xcdm_group_kernel(raw);
     hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes);
     if (e != hipSuccess) return e;
     int n = 0;

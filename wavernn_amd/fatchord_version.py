@@ -418,7 +418,8 @@ class WaveRNN(nn.Module):
 
     # --------------------------------------------------------------------- streaming
     def stream(self, n_streams: int = 1, total_frames: Optional[int] = None, *, noise=None,
-               seed: Optional[int] = None, row_offset: int = 0, wide: bool = False) -> "WaveRNNStream":
+               seed: Optional[int] = None, row_offset: int = 0, wide: bool = False,
+               mu_law: bool = True) -> "WaveRNNStream":
         """A streaming session: push mel frames as the acoustic model produces them, get the audio
         that has become final — unbatched MoL generate() in pieces, the recurrent state kept on the
         GPU between pushes (C-ABI wrnn_stream_*).  `n_streams` utterances (1..8) advance in lock
@@ -443,8 +444,15 @@ class WaveRNN(nn.Module):
         oracle, and with `seed` equals generate(seed=, row_offset=) within MOL tolerance.  It is
         NOT bit-identical to the same session opened narrow (another kernel, sums associated
         differently), and the members' conditioning is not batched across sessions: callers who can
-        lock-step should open one U-wide session."""
-        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset, wide)
+        lock-step should open one U-wide session.
+
+        A RAW model (9 bits, rnn / fc 512) streams through wide sessions only (`wide=True`; narrow
+        RAW raises NotImplementedError, as do other bit depths and dims): the many-row kernel's
+        softmax head, whose class labels are those of generate() on the same draws bit for bit.
+        `noise` is then [steps][n_streams][512] Exp(1) draws by absolute step, the layout
+        generate(noise=) takes; `mu_law` (default True, as generate_many) expands the emitted samples
+        as generate(mu_law=) does and is ignored for MoL models."""
+        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset, wide, mu_law)
 
     def push_streams(self, pushes) -> list:
         """Advance several sessions of this model in one call: `pushes` is a sequence of
@@ -473,11 +481,12 @@ class WaveRNN(nn.Module):
         return [w.cpu().numpy() for w in members[0][0].loop.push_streams(members)]
 
     def generate_stream(self, mels, chunk_frames: int = 8, *, noise=None, seed: Optional[int] = None,
-                        row_offset: int = 0, wide: bool = False):
+                        row_offset: int = 0, wide: bool = False, mu_law: bool = True):
         """generate(mels, None, False, ...) as a generator of float64 chunks, for a mel known up
         front: mels [1][feat][T] (or [U][feat][T], chunks [U][m]) pushed `chunk_frames` at a time
         (or by the frame counts of a sequence).  The chunks concatenate to generate()'s output.
-        `wide` is passed to stream(): up to 128 utterances in lock step on the many-row kernel."""
+        `wide` is passed to stream(): up to 128 utterances in lock step on the many-row kernel.
+        `mu_law` likewise: a RAW model streams wide only, its samples mu-law expanded by default."""
         device = next(self.parameters()).device
         mels = torch.as_tensor(mels, device=device).to(torch.float32)
         if mels.dim() != 3:
@@ -486,7 +495,7 @@ class WaveRNN(nn.Module):
         counts = [chunk_frames] * (-(-T // chunk_frames)) if isinstance(chunk_frames, int) else list(chunk_frames)
         if any(c < 1 for c in counts):
             raise ValueError("chunk_frames must be positive")
-        with self.stream(U, T, noise=noise, seed=seed, row_offset=row_offset, wide=wide) as s:
+        with self.stream(U, T, noise=noise, seed=seed, row_offset=row_offset, wide=wide, mu_law=mu_law) as s:
             f = 0
             for c in counts:
                 if f >= T:
@@ -598,7 +607,7 @@ class WaveRNNStream:
     WaveRNN.push_streams advances several sessions in one call, each at its own pace."""
 
     def __init__(self, model: WaveRNN, n_streams: int, total_frames: Optional[int], noise, seed: Optional[int],
-                 row_offset: int, wide: bool = False):
+                 row_offset: int, wide: bool = False, mu_law: bool = True):
         if wide and not 1 <= int(n_streams) <= 128:
             raise ValueError(f"a wide session has 1..128 utterances, not {n_streams!r}")
         device = next(model.parameters()).device
@@ -614,7 +623,7 @@ class WaveRNNStream:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         cfg, packed = model._melresnet_packed()
         self._session = FatchordStream(model.loop_handle(), model._upsample_spec(), cfg, packed, n_streams,
-                                       total_frames, nz, seed, row_offset, wide=wide)
+                                       total_frames, nz, seed, row_offset, wide=wide, mu_law=bool(mu_law))
         self.wide = bool(wide)
         self.n_streams = n_streams
         self.lookahead_frames = self._session.lookahead_frames
@@ -626,6 +635,10 @@ class WaveRNNStream:
         if mel.dim() == 2:
             mel = mel[None]
         return mel.contiguous()
+
+    def set_mu_law(self, on: bool) -> None:
+        """RAW sessions, before the first push: switch the mu-law expansion of the emitted samples."""
+        self._session.set_mu_law(on)
 
     def push(self, mel_chunk) -> np.ndarray:
         return self._session.push(self._mel_tensor(mel_chunk)).cpu().numpy()

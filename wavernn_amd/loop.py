@@ -494,6 +494,17 @@ def wide_plan(steps, rows, steps_per_launch: int) -> list:
     return plan
 
 
+def wide_steps_per_launch(rows: int, longest_steps: int, raw: bool = False) -> int:
+    """Steps per persistent launch of a wide push with `rows` rows to run, the longest member
+    `longest_steps` steps (C-ABI wrnn_wide_steps_per_launch, host only; reads WRNN_TERMS_MB as the
+    push does): the terms budget over rows · 4608 floats per step, for a RAW loop over
+    rows · (4608 + 512) — its draws share the budget.  The steps_per_launch of wide_plan."""
+    n = nat.lib().wrnn_wide_steps_per_launch(int(rows), int(longest_steps), int(bool(raw)))
+    if n < 0:
+        nat.check_cond(n)
+    return n
+
+
 def list_plan(frames, lanes: Optional[int] = None) -> Tuple[list, list, list]:
     """The lane schedule of a list call (C-ABI wrnn_list_plan, host only): (lane_of, pos_in_lane,
     lane_frames) for utterances of `frames` frames on `lanes` lanes (default min(8, len(frames))):
@@ -532,11 +543,17 @@ class FatchordStream:
     7): `n_streams` 1..128, and groups of wide sessions hold up to 128 rows.  A wide member's audio
     is bit-identical whatever its company (every wide launch is the kernel's four-quad form, whose
     batch rows are independent MFMA columns) and lies within the project's bound of the oracle; it
-    is NOT bit-identical to the same session opened narrow, which runs another kernel."""
+    is NOT bit-identical to the same session opened narrow, which runs another kernel.
+
+    A RAW loop (9 bits, rnn / fc 512) opens wide sessions only: `noise` is then
+    [steps][n_streams][512] Exp(1) draws by absolute step (generate()'s layout), the class labels
+    are those of generate() on the same draws bit for bit, and `mu_law=True` expands the emitted
+    samples (C-ABI wrnn_stream_mu_law; ignored on a MoL loop; set_mu_law() changes it before the
+    first push)."""
 
     def __init__(self, loop: FatchordLoop, spec, mr_cfg, mr_packed: torch.Tensor, n_streams: int = 1,
                  total_frames: Optional[int] = None, noise: Optional[torch.Tensor] = None, seed: int = 0,
-                 row_offset: int = 0, wide: bool = False):
+                 row_offset: int = 0, wide: bool = False, mu_law: bool = False):
         self._s = None
         self.wide = bool(wide)
         if self.wide and not 1 <= int(n_streams) <= WIDE_ROWS:
@@ -569,6 +586,18 @@ class FatchordStream:
         nat.check(loop._h, rc)
         self._s = s
         loop._sessions.add(self)
+        if mu_law and loop.mode == "RAW":
+            self.set_mu_law(True)
+
+    def set_mu_law(self, on: bool) -> None:
+        """Mu-law expansion of the emitted samples (C-ABI wrnn_stream_mu_law): a RAW session, before
+        its first push.  ValueError (the session unchanged) on a MoL session or after a push."""
+        if self._s is None:
+            raise RuntimeError("the session is closed")
+        rc = nat.lib().wrnn_stream_mu_law(self._s, int(bool(on)))
+        if rc == -1:   # WRNN_EINVAL
+            raise ValueError((nat.lib().wrnn_last_error(self.loop._h) or b"").decode(errors="replace"))
+        nat.check(self.loop._h, rc)
 
     def plan(self, frames: int, final: bool = False) -> int:
         """Samples per utterance the session will have emitted in all once `frames` frames are in."""
