@@ -509,6 +509,84 @@ int wrnn_generate_list(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *co
                        const int *T, int U, int lanes, const float *const *noise, uint64_t seed, int64_t row_offset,
                        float *const *out, void *stream);
 
+/* ---- Wide lists: a list on up to 128 many-row slots, MoL and RAW (wide-list addition, same ABI) --
+ * The one-shot use of the grouped many-row launches of wide sessions: up to 128 SLOTS, 16 per XCD,
+ * each running a queue of whole utterances back to back; when an utterance ends its slot goes on
+ * with the next of its queue.  The entry a batch of hundreds of sentences calls; the only list form
+ * for RAW (9 bits) models.
+ *
+ * Schedule (wrnn_list_wide_plan; host only, stateless, deterministic).  Assignment: the rule of
+ * wrnn_list_plan with `slots` in 1..128 — utterances by decreasing frame count (ties: the lower
+ * index first), each to the least loaded slot (ties: the lowest slot); a slot runs its utterances in
+ * the order they were assigned.  Launch cuts: a slot's timeline is the concatenation of its
+ * utterances' steps (hop per frame).  All rows of a grouped launch run the same number of steps and
+ * the kernel takes no per-row mask, so the common timeline is cut at EVERY utterance end on ANY
+ * slot, and each piece between two such cuts again into launches of at most
+ * wrnn_wide_steps_per_launch(rows, longest timeline in steps, raw) steps (the WRNN_TERMS_MB budget).
+ * Lengths are multiples of hop, so no utterance-boundary cut leaves a launch shorter than a frame.
+ * The rows of a launch are the slots that still have a step to run, compacted in slot order:
+ * launch row r on XCD r % 8, slot r / 8 there; a slot whose queue has ended takes no row.
+ *   frames       [U]      frame counts T_i, each >= 21
+ *   slots, hop            1..128; steps per frame (>= 1)
+ *   raw                   0: MoL budget, 1: RAW budget (the 512 draws share it)
+ *   slot_of      [U]      out: the slot of utterance i             (may be NULL, as every output)
+ *   pos_in_slot  [U]      out: its place in that slot's queue
+ *   slot_frames  [slots]  out: the slot's timeline in frames
+ *   launch_first / launch_steps / launch_rows [cap]  out: per launch its first timeline step, its
+ *                         steps and its rows (the first `cap` launches)
+ * Returns the number of launches; a negative WRNN_EINVAL (message in wrnn_cond_last_error) for
+ * U < 1, slots outside 1..128, hop < 1, any T_i < 21, or a timeline past 2^31 − 1 steps.
+ *
+ * wrnn_generate_list_wide: the arguments of wrnn_generate_list with `slots` (1..128; 0: min(128, U))
+ * in place of `lanes`; noise[i] is [hop·T_i][K] by the utterance's own step, K = 11 MoL uniforms or
+ * 512 Exp(1) draws for RAW.  It takes a handle wrnn_stream_open_wide would take (MoL or RAW 9 bits,
+ * rnn / fc 512, the four-quad grouped form co-resident) and returns WRNN_EUNSUPPORTED with that
+ * call's messages otherwise; deepmind handles are refused.  Each utterance's frame-term stores are
+ * computed with the launches and shapes of its single many-row call (never one GEMM over several
+ * utterances); then the plan's launches run with the sequence of a wide push — per launch one
+ * interpolation launch, one draws launch, the hop-area reset, the member counters, one persistent
+ * grouped launch.  The row table of the whole call goes up once from pinned memory, every workspace
+ * is grown before anything is queued and nothing waits on the stream between launches.  A launch
+ * row is its utterance at its own step: stores at base 0, Philox row row_offset + i, a state record
+ * that belongs to the utterance and to this call (neither a session's nor a one-shot call's), zero
+ * state at the utterance's step 0.  Every argument of every utterance is checked before anything is
+ * queued (WRNN_EINVAL: the handle is as before).  Sessions (narrow and wide) and one-shot calls on
+ * the same handle may run before and after it in stream order.  Sets wrnn_info.last_path to 7 and
+ * the timing events around the loop share (interpolation, draws, resets, persistent launches), as
+ * a wide push does.
+ *
+ * What a wide list promises.
+ *   Independence of company: out[i] does not depend on the other utterances, their order, `slots`
+ *     or WRNN_TERMS_MB — it is bit-identical to the wide list that holds utterance i alone, called
+ *     with row_offset + i (every grouped launch is the four-quad form: rows are independent MFMA
+ *     columns).
+ *   MoL: within 2·MOL_TOL = 2e-5 of the oracle on the same draws (the wide bound); under Philox within
+ *     MOL_TOL of wrnn_generate_frames of utterance i with (seed, row_offset + i).  NOT bit-identical
+ *     to wrnn_generate_list or wrnn_generate_frames: another kernel.
+ *   RAW: the class labels are the oracle's and wrnn_generate's on the same draws, bit for bit, so
+ *     without mu-law expansion every sample before the fade is exact. */
+int wrnn_list_wide_plan(const int *frames, int U, int slots, int hop, int raw, int *slot_of, int *pos_in_slot,
+                        int64_t *slot_frames, int *launch_first, int *launch_steps, int *launch_rows, int cap);
+int wrnn_generate_list_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *mel, const float *const *aux,
+                            const int *T, int U, int slots, const float *const *noise, uint64_t seed, int64_t row_offset,
+                            float *const *out, void *stream);
+
+/* wrnn_postprocess (unbatched) for every utterance of a list in ONE launch: entry i is utterance i's
+ * fp32 loop output y [steps] (device), its wave_len (fade_len <= wave_len <= steps) and the offset
+ * dst of its float64 waveform in `wave`; the optional mu-law expansion (RAW; mu = n_classes − 1, by
+ * wrnn_postprocess's expression) comes before the 20-frame fade-out.  wave[dst .. dst + wave_len)
+ * equals wrnn_postprocess(y, 1, steps, 0, 0, mu_law, n_classes, wave_len, fade_len, …) bit for bit
+ * (with mu-law on: to the accuracy of pow, rtol 1e-12).  One copy then brings all waveforms to the
+ * host.  `entries` [U] lives in device memory; max_wave_len >= every wave_len sizes the grid.
+ * WRNN_EINVAL for U outside 1..65535, fade_len < 1 or max_wave_len < fade_len. */
+typedef struct {
+    const float *y;
+    int64_t dst;
+    int32_t steps, wave_len;
+} wrnn_post_entry;
+int wrnn_postprocess_list(const wrnn_post_entry *entries, int U, int max_wave_len, int mu_law, int n_classes,
+                          int fade_len, double *wave, void *stream);
+
 /* Message of the last failed stateless call on this thread. */
 const char *wrnn_cond_last_error(void);
 

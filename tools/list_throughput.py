@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Throughput of a list of utterances of unequal length (a TTS batch) on the headline model (MoL
-rnn/fc 512), three ways in one process:
+rnn/fc 512), four ways in one process:
 
-    python tools/list_throughput.py [--reps 3] [--utterances 24] [--sparse] [--out FILE]
+    python tools/list_throughput.py [--reps 3] [--utterances 24] [--ways abcd] [--sparse | --raw] [--out FILE]
 
   (a) one generate() per utterance, one after the other;
   (b) generate_many(list): every row runs for the longest member's steps, conditioning at sample rate;
-  (c) generate_list(list): the eight XCDs as lanes, each a queue of utterances (wrnn_generate_list).
+  (c) generate_list(list): the eight XCDs as lanes, each a queue of utterances (wrnn_generate_list);
+  (d) generate_list(list, wide=True): up to 128 many-row slots, each a queue (wrnn_generate_list_wide).
 The list: `--utterances` (default 24) mels of 101 … 401 frames, lengths and contents from fixed seeds.
 Beside it, eight equal utterances of 401 frames through (b) and (c): the same eight rows, one per
 XCD, 401·hop steps each — what the piece walk costs inside the step loop, if anything.
@@ -18,8 +19,14 @@ the loop's timing events (frame terms + per-round interpolation + persistent lau
 is MelResNet, host work and the float64 post), the persistent launches per call (restated from the
 launch loops of csrc/capi.cpp for the WRNN_TERMS_MB in effect), and for (c) the lane occupancy
 Σ L_i / (lanes · longest lane timeline) and the MelResNet (frames()) time of the list measured on
-its own.  (a) and (c) must produce identical audio.  --sparse: the 95 %-pruned rnn-896 model.  One
-JSON line per row; --out appends them to a file as well."""
+its own.  (a) and (c) must produce identical audio; (d) runs another kernel: its largest difference
+from the first other way that ran is reported.  For (d): the slots, the slot occupancy Σ steps /
+(slots · longest slot timeline), and the share of its loop time that is not steps — (loop − Σ launch
+steps × 11.9 µs, the wide step of DESIGN §4.4c) / loop.  A way the device cannot hold (generate_many
+builds a sample-rate [L_max][rows][208] tensor) is recorded as refused with the error's text; with
+--many-block N, (b) runs the list N utterances at a time, one generate_many after the other.
+--sparse: the 95 %-pruned rnn-896 model.  --raw: the RAW 9-bit rnn / fc 512 model (mu-law off), which
+has ways (a) and (d) only.  One JSON line per row; --out appends them to a file as well."""
 import argparse
 import json
 import math
@@ -35,12 +42,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from wavernn_amd import synthetic as syn                     # noqa: E402
 from wavernn_amd.fatchord_version import WaveRNN             # noqa: E402
-from wavernn_amd.loop import list_plan                       # noqa: E402
+from wavernn_amd.loop import list_plan, list_wide_plan       # noqa: E402
 from wavernn_amd.pruning import prune_state                  # noqa: E402
 
 N_XCD = 32 * 160       # terms per row and step of the one-row XCD kernel (csrc/fatchord_xcd.h)
 N_XCDS = 32 * 228      # … of the block-sparse rnn-896 one-row kernel (csrc/fatchord_xcds.h)
 N_XCDM = 32 * 144      # … of the many-row kernel (csrc/fatchord_xcdm.h: kMRing)
+WIDE_STEP_US = 11.9    # the measured step of a full wide launch
 
 
 def _budget():
@@ -77,7 +85,7 @@ def _wall(fn, dev):
     return out, (time.perf_counter() - t0) * 1e3
 
 
-def run_case(model, d, mels, ways, reps, dev, what, emit):
+def run_case(model, d, mels, ways, reps, dev, what, emit, many_block=0):
     frames = [int(m.shape[2]) for m in mels]
     hop, U = d.hop_length, len(mels)
     kxc = d.feat_dims + d.res_out_dims + 4
@@ -95,14 +103,25 @@ def run_case(model, d, mels, ways, reps, dev, what, emit):
         return out, ms
 
     def many():
-        out = model.generate_many(mels, None, False, 11000, 550, False, seed=seed)
-        return out, loop.elapsed_ms()
+        if not many_block or many_block >= U:
+            out = model.generate_many(mels, None, False, 11000, 550, False, seed=seed)
+            return out, loop.elapsed_ms()
+        out, ms = [], 0.0
+        for b0 in range(0, U, many_block):      # the list in blocks: one generate_many after the other
+            out += model.generate_many(mels[b0:b0 + many_block], None, False, 11000, 550, False, seed=seed, row_offset=b0)
+            ms += loop.elapsed_ms()
+        return out, ms
 
     def lst():
         out = model.generate_list(mels, seed=seed)
         return out, loop.elapsed_ms()
 
-    fns = {"a": ("one generate() per utterance", single), "b": ("generate_many", many), "c": ("generate_list", lst)}
+    def wide():
+        out = model.generate_list(mels, seed=seed, wide=True, mu_law=False)
+        return out, loop.elapsed_ms()
+
+    fns = {"a": ("one generate() per utterance", single), "b": ("generate_many", many), "c": ("generate_list", lst),
+           "d": ("generate_list(wide=True)", wide)}
     audio, wall, dev_ms, path, refused = {}, {w: [] for w in ways}, {w: [] for w in ways}, {}, {}
     for rep in range(reps + 1):          # rep 0: the untimed warm-up of every shape
         for w in ways:
@@ -110,8 +129,9 @@ def run_case(model, d, mels, ways, reps, dev, what, emit):
                 continue
             try:
                 (out, lms), ms = _wall(fns[w][1], dev)
-            except NotImplementedError as e:
-                refused[w] = str(e)
+            except (NotImplementedError, torch.cuda.OutOfMemoryError) as e:
+                refused[w] = f"{type(e).__name__}: {e}".splitlines()[0]
+                torch.cuda.empty_cache()
                 continue
             path[w] = loop.info["last_path"]
             audio[w] = out
@@ -120,6 +140,10 @@ def run_case(model, d, mels, ways, reps, dev, what, emit):
                 dev_ms[w].append(lms)
     if "a" in audio and "c" in audio:
         assert all(np.array_equal(x, y) for x, y in zip(audio["a"], audio["c"])), "generate_list differs from the single calls"
+    wide_delta = None
+    other = next((w for w in ("a", "c", "b") if w in audio), None)
+    if "d" in audio and other:
+        wide_delta = max(float(np.abs(x - y).max()) for x, y in zip(audio["d"], audio[other]))
     mr = []
     for rep in range(reps + 1):
         _, ms = _wall(lambda: [model.frames(m) for m in mels], dev)
@@ -147,7 +171,22 @@ def run_case(model, d, mels, ways, reps, dev, what, emit):
             row["persistent_launches"] = launches_many(L_max, U, kxc, N) if U > 8 or equal else \
                 sum(launches_single(L_max, min(8, U - b0), kxc, N) for b0 in range(0, U, 8))
             row["row_steps_run"] = U * L_max
+            if many_block and many_block < U:
+                row["measured_in_blocks_of"] = many_block
             row["loop_us_per_step_of_the_longest_row"] = round(statistics.median(dev_ms[w]) * 1e3 / L_max, 4)
+        elif w == "d":
+            raw = d.mode == "RAW"
+            _, _, slot_frames, ls = list_wide_plan(frames, None, hop=hop, raw=raw)
+            longest, loop_ms = max(slot_frames) * hop, statistics.median(dev_ms[w])
+            assert sum(s for _, s, _ in ls) == longest
+            row.update({"persistent_launches": len(ls), "slots": len(slot_frames), "longest_slot_steps": longest,
+                        "slot_occupancy": round(steps / (len(slot_frames) * longest), 4),
+                        "launch_steps_min_median_max": [min(s for _, s, _ in ls), int(statistics.median(s for _, s, _ in ls)),
+                                                        max(s for _, s, _ in ls)],
+                        "loop_us_per_step_of_the_longest_slot": round(loop_ms * 1e3 / longest, 4),
+                        "not_steps_share_of_loop": round((loop_ms - longest * WIDE_STEP_US * 1e-3) / loop_ms, 4),
+                        "max_abs_diff_from": {"way": fns[other][0], "value": wide_delta} if other else None,
+                        "melresnet_ms": round(statistics.median(mr), 2)})
         else:
             n, longest = launches_list(frames, lanes, hop, N)
             row.update({"persistent_launches": n, "lanes": lanes, "longest_lane_steps": longest,
@@ -162,13 +201,17 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--utterances", type=int, default=24)
     ap.add_argument("--sparse", action="store_true", help="the 95 %%-pruned rnn-896 model")
+    ap.add_argument("--raw", action="store_true", help="the RAW 9-bit rnn / fc 512 model: ways (a) and (d)")
+    ap.add_argument("--ways", default=None, help="the ways to run, e.g. bcd (default abcd; --raw: ad; --sparse: abc)")
+    ap.add_argument("--many-block", type=int, default=0, help="(b) in blocks of this many utterances")
+    ap.add_argument("--skip-equal", action="store_true", help="leave out the eight equal utterances")
     ap.add_argument("--skip-single", action="store_true", help="leave out (a), the slowest way")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("list_throughput.py times the GPU path: no GPU visible")
     dev = torch.device("cuda", 0)
-    d = syn.SPARSE896_MOL if args.sparse else syn.DEFAULT_MOL
+    d = syn.SPARSE896_MOL if args.sparse else syn.DEFAULT_RAW if args.raw else syn.DEFAULT_MOL
     state = syn.make_fatchord_state(d, 0)
     if args.sparse:
         state = prune_state(state, 0.95)
@@ -187,8 +230,14 @@ def main():
     lengths = [401 if U == 1 else 101 + round(i * 300 / (U - 1)) for i in range(U)]
     np.random.default_rng(24).shuffle(lengths)       # arrival order, not sorted
     mixed = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=10 + i))[None].to(dev) for i, T in enumerate(lengths)]
-    ways = ("b", "c") if args.skip_single else ("a", "b", "c")
-    run_case(model, d, mixed, ways, args.reps, dev, "mixed list, 101..401 frames" + (", sparse rnn 896" if args.sparse else ""), emit)
+    ways = tuple(args.ways) if args.ways else ("a", "d") if args.raw else ("a", "b", "c") if args.sparse else ("a", "b", "c", "d")
+    if args.skip_single:
+        ways = tuple(w for w in ways if w != "a")
+    tag = ", sparse rnn 896" if args.sparse else ", RAW 9-bit" if args.raw else ""
+    run_case(model, d, mixed, ways, args.reps, dev, "mixed list, 101..401 frames" + tag, emit, args.many_block)
+    if args.raw or args.skip_equal:
+        model.train()
+        return
     equal = [torch.from_numpy(syn.make_mel(d.feat_dims, 401, seed=100 + i))[None].to(dev) for i in range(8)]
     run_case(model, d, equal, ("b", "c"), args.reps, dev, "eight equal utterances of 401 frames" + (", sparse rnn 896" if args.sparse else ""), emit)
     model.train()

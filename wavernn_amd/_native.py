@@ -23,7 +23,8 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_melresnet_tile_frames", "wrnn_stream_open", "wrnn_stream_push", "wrnn_stream_plan",
            "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint",
            "wrnn_list_plan", "wrnn_generate_list", "wrnn_stream_open_wide", "wrnn_wide_plan",
-           "wrnn_stream_mu_law", "wrnn_wide_steps_per_launch")
+           "wrnn_stream_mu_law", "wrnn_wide_steps_per_launch", "wrnn_list_wide_plan", "wrnn_generate_list_wide",
+           "wrnn_postprocess_list")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -145,6 +146,15 @@ def lib() -> ctypes.CDLL:
     L.wrnn_generate_list.argtypes = [vp, ctypes.POINTER(UpsampleCfg), ctypes.POINTER(vp), ctypes.POINTER(vp), pi, i32, i32,
                                      ctypes.POINTER(vp), u64, i64, ctypes.POINTER(vp), vp]
     L.wrnn_generate_list.restype = i32
+    # frames [U], U, slots, hop, raw → slot_of [U], pos_in_slot [U], slot_frames [slots], launch_first / steps / rows [cap], cap
+    L.wrnn_list_wide_plan.argtypes = [pi, i32, i32, i32, i32, pi, pi, ctypes.POINTER(i64), pi, pi, pi, i32]
+    L.wrnn_list_wide_plan.restype = i32
+    # wrnn_generate_list's arguments with slots (0: min(128, U)) in place of lanes
+    L.wrnn_generate_list_wide.argtypes = L.wrnn_generate_list.argtypes
+    L.wrnn_generate_list_wide.restype = i32
+    # entries [U] (device), U, max_wave_len, mu_law, n_classes, fade_len, wave (device), stream
+    L.wrnn_postprocess_list.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
+    L.wrnn_postprocess_list.restype = i32
     L.wrnn_fingerprint.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i64), i32, vp, vp]
     L.wrnn_fingerprint.restype = i32
     L.wrnn_cond_last_error.argtypes = []

@@ -166,3 +166,35 @@ def postprocess(y: torch.Tensor, batched: bool, overlap: int, mu_law: bool, n_cl
     nat.check_cond(nat.lib().wrnn_postprocess(y.data_ptr(), rows, steps, int(batched), overlap, int(mu_law),
                                               n_classes, wave_len, fade_len, wave.data_ptr(), _stream(y.device)))
     return wave
+
+
+POST_ENTRY = np.dtype([("y", np.uint64), ("dst", np.int64), ("steps", np.int32), ("wave_len", np.int32)])
+
+
+def postprocess_list(ys, wave_lens, mu_law: bool, n_classes: int, fade_len: int) -> Tuple[torch.Tensor, list]:
+    """The unbatched postprocess of every utterance of a list in one launch (C-ABI
+    wrnn_postprocess_list): ys[i] [steps_i] fp32 loop output on the GPU, wave_lens[i] its waveform
+    length → (one float64 device buffer, the utterances' offsets in it): utterance i's waveform is
+    buffer[off_i : off_i + wave_lens[i]], what postprocess(ys[i][None], False, 0, mu_law, n_classes,
+    wave_lens[i], fade_len) gives (bit for bit; with mu-law on to pow's accuracy)."""
+    ys = [y.contiguous().float() for y in ys]
+    _need_gpu(*ys)
+    wave_lens = [int(w) for w in wave_lens]
+    if not ys or len(ys) != len(wave_lens):
+        raise ValueError("ys and wave_lens hold one entry per utterance, at least one")
+    tab = np.zeros(len(ys), POST_ENTRY)
+    off, total = [], 0
+    for i, (y, w) in enumerate(zip(ys, wave_lens)):
+        if y.dim() != 1 or w > y.shape[0]:
+            raise ValueError(f"ys[{i}] must be a [steps] tensor of at least wave_len = {w} steps")
+        if fade_len > w:
+            raise ValueError(f"operands could not be broadcast together with shapes ({w},) ({fade_len},) ")
+        tab[i] = (y.data_ptr(), total, y.shape[0], w)
+        off.append(total)
+        total += w
+    dev = ys[0].device
+    d_tab = torch.from_numpy(tab.view(np.uint8)).to(dev)
+    wave = torch.empty(total, device=dev, dtype=torch.float64)
+    nat.check_cond(nat.lib().wrnn_postprocess_list(d_tab.data_ptr(), len(ys), max(wave_lens), int(mu_law), n_classes,
+                                                   fade_len, wave.data_ptr(), _stream(dev)))
+    return wave, off

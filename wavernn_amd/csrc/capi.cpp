@@ -2974,6 +2974,29 @@ void wrnn_stream_close(wrnn_stream_t *s) {
     delete s;
 }
 
+// Why a MoL or RAW handle has no grouped many-row form (wrnn_stream_open_wide and
+// wrnn_generate_list_wide refuse it with WRNN_EUNSUPPORTED and this text), or "" when it has one
+static std::string wide_refusal(const wrnn_t *h) {
+    if (h->cfg.mode == WRNN_MODE_RAW) {   // the many-row kernel's softmax head: which of its conditions this handle misses
+        if (h->cfg.n_classes != kMRawNC)
+            return "wide RAW streaming sessions run the many-row XCD kernel's softmax head of " + std::to_string(kMRawNC) +
+                   " classes (bits = 9): this handle has " + std::to_string(h->cfg.n_classes) + " classes";
+        if (h->cfg.rnn_dims != 512 || h->cfg.fc_dims != 512)
+            return "wide RAW streaming sessions run the many-row XCD kernel (rnn / fc 512): this handle has rnn " +
+                   std::to_string(h->cfg.rnn_dims) + ", fc " + std::to_string(h->cfg.fc_dims);
+        if (!(h->xcdm_ok && h->xcdm_nq >= kMQuadMax))
+            return "wide RAW streaming sessions run the many-row XCD kernel with four co-resident quads per XCD (aux 32, a "
+                   "full MI355X): this handle does not have the four-quad form";
+        if (!h->xcdmg_ok)
+            return "wide RAW streaming sessions run the many-row XCD kernel's grouped RAW instantiation: it is not "
+                   "co-resident on this device";
+    }
+    if (!(h->xcdm_ok && h->xcdmg_ok && h->xcdm_nq >= kMQuadMax))
+        return "wide streaming sessions run the many-row XCD kernel with four co-resident quads per XCD (MoL, rnn / fc "
+               "512, a full MI355X): this handle does not have it";
+    return std::string();
+}
+
 static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
                        const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
                        uint64_t seed, int64_t row_offset, wrnn_stream_t **out, bool wide) {
@@ -2990,27 +3013,10 @@ static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melr
     const bool raw = !h->dm && h->cfg.mode == WRNN_MODE_RAW;
     if (h->dm || (h->cfg.mode != WRNN_MODE_MOL && !(raw && wide)))
         return fail(h, WRNN_EUNSUPPORTED, "streaming sessions run the one-row XCD MoL kernels: this handle is not MoL");
-    if (raw) {   // the many-row kernel's softmax head: which of its conditions this handle misses
-        if (h->cfg.n_classes != kMRawNC)
-            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel's softmax head of " +
-                                                  std::to_string(kMRawNC) + " classes (bits = 9): this handle has " +
-                                                  std::to_string(h->cfg.n_classes) + " classes");
-        if (h->cfg.rnn_dims != 512 || h->cfg.fc_dims != 512)
-            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel (rnn / fc 512): this "
-                                              "handle has rnn " + std::to_string(h->cfg.rnn_dims) + ", fc " +
-                                                  std::to_string(h->cfg.fc_dims));
-        if (!(h->xcdm_ok && h->xcdm_nq >= kMQuadMax))
-            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel with four co-resident "
-                                              "quads per XCD (aux 32, a full MI355X): this handle does not have the "
-                                              "four-quad form");
-        if (!h->xcdmg_ok)
-            return fail(h, WRNN_EUNSUPPORTED, "wide RAW streaming sessions run the many-row XCD kernel's grouped RAW "
-                                              "instantiation: it is not co-resident on this device");
+    if (wide) {
+        const std::string why = wide_refusal(h);
+        if (!why.empty()) return fail(h, WRNN_EUNSUPPORTED, why);
     }
-    if (wide && !(h->xcdm_ok && h->xcdmg_ok && h->xcdm_nq >= kMQuadMax))
-        return fail(h, WRNN_EUNSUPPORTED,
-                    "wide streaming sessions run the many-row XCD kernel with four co-resident quads per XCD (MoL, rnn / fc "
-                    "512, a full MI355X): this handle does not have it");
     const LoopPath path = wide ? P_XCDM : choose_path(h, U);
     if (!wide && path != P_XCD && path != P_XCDS)
         return fail(h, WRNN_EUNSUPPORTED,
@@ -3376,6 +3382,70 @@ int wrnn_wide_plan(const int *steps, const int *rows, int count, int steps_per_l
     return (int)ls.size();
 }
 
+// The device row table and its pinned staging copy, sized for `ntab` records; returns once the last
+// upload has read the staging copy, so the caller may rewrite it.
+static int wide_tab_reserve(wrnn_t *h, size_t ntab) {
+    HIP_TRY(h, ensure(h->d_wtab, h->wtab_cap, ntab));
+    if (!h->d_members) HIP_TRY(h, hipMalloc(&h->d_members, kXcds * sizeof(int)));
+    HIP_TRY(h, hipEventSynchronize(h->ev_wtab));   // the last push's upload has read the staging copy
+    if (ntab > h->hwtab_cap) {
+        if (h->h_wtab) HIP_TRY(h, hipHostFree(h->h_wtab));
+        h->h_wtab = nullptr;
+        h->hwtab_cap = 0;
+        HIP_TRY(h, hipHostMalloc((void **)&h->h_wtab, 2 * ntab * sizeof(XcdmRow), hipHostMallocDefault));
+        h->hwtab_cap = 2 * ntab;
+    }
+    return WRNN_OK;
+}
+
+// The launch loop of a wide push and of a wide list: the `ntab` records of h_wtab (the launches' row
+// tables one after the other) go up once, then per launch one interpolation launch into the shared
+// terms, one draws launch, the hop area reset, the member counters and one persistent launch.  The
+// workspaces are grown already; nothing here waits on the stream.
+static int wide_run_launches(wrnn_t *h, const std::vector<WideLaunch> &ls, size_t ntab, const float *d_coef, int hop,
+                             int nJ, bool raw, int K, hipStream_t st) {
+    const int N = kXcdWgs * kMRing;
+    // ---- queuing begins
+    HIP_TRY(h, hipMemcpyAsync(h->d_wtab, h->h_wtab, ntab * sizeof(XcdmRow), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipEventRecord(h->ev_wtab, st));
+    HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
+    h->last_path = (int)P_XCDM;
+    // wrnn_elapsed_ms: the loop share of this push (interpolation, draws, resets and persistent
+    // launches of all its rounds), so a caller can split a tick into conditioning and loop
+    HIP_TRY(h, hipEventRecord(h->ev0, st));
+    size_t at = 0;
+    for (const WideLaunch &l : ls) {
+        const XcdmRow *tab = h->d_wtab + at;
+        at += (size_t)l.rows;
+        HIP_TRY(h, launch_terms_interp_wide(tab, d_coef, h->d_T, N, hop, nJ, l.rows, l.Lc, st));
+        HIP_TRY(h, launch_draws_wide(h->d_xmnoise, tab, l.rows, l.Lc, K, raw ? 0 : 1, st));
+        // every packed hop element empty, every tag one no step carries (fatchord_xcdm.h)
+        HIP_TRY(h, hipMemsetAsync(h->d_xmxg, 0xFF, (size_t)kXcds * kMXcdStride * 8, st));
+        HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
+        XcdmArgs a{};
+        a.slab = h->d_xmslab;
+        a.terms = h->d_T;
+        a.noise = h->d_xmnoise;
+        a.nz_ts = l.rows;
+        a.nz_t0 = 0;
+        a.nz_b0 = 0;
+        a.xg = h->d_xmxg;
+        a.members = h->d_members;
+        a.ctl = h->d_ctl;
+        a.timeout_ticks = h->timeout_ticks;
+        a.t0 = 0;
+        a.Lc = l.Lc;
+        a.Bt = l.rows;
+        a.nb = l.rows;
+        a.s = h->xms;
+        a.rows = tab;
+        HIP_TRY(h, launch_xcdm_group(a, raw, st));
+    }
+    HIP_TRY(h, hipEventRecord(h->ev1, st));
+    h->timed = true;
+    return WRNN_OK;
+}
+
 // Per launch of the plan: the row table (uploaded once for the whole push), one interpolation launch
 // into the shared terms, one draws launch, the hop area reset to all-ones (tags and slot parities
 // restart at every launch), the membership counters, one persistent launch.  Nothing here outlives
@@ -3404,16 +3474,7 @@ static int wide_group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPu
     if (grow(h, h->d_T, h->T_cap, (size_t)(Lc_max + 1) * rows * N) ||
         grow(h, h->d_xmnoise, h->xmnoise_cap, (size_t)Lc_max * rows * K))
         return WRNN_EHIP;
-    HIP_TRY(h, ensure(h->d_wtab, h->wtab_cap, ntab));
-    if (!h->d_members) HIP_TRY(h, hipMalloc(&h->d_members, kXcds * sizeof(int)));
-    HIP_TRY(h, hipEventSynchronize(h->ev_wtab));   // the last push's upload has read the staging copy
-    if (ntab > h->hwtab_cap) {
-        if (h->h_wtab) HIP_TRY(h, hipHostFree(h->h_wtab));
-        h->h_wtab = nullptr;
-        h->hwtab_cap = 0;
-        HIP_TRY(h, hipHostMalloc((void **)&h->h_wtab, 2 * ntab * sizeof(XcdmRow), hipHostMallocDefault));
-        h->hwtab_cap = 2 * ntab;
-    }
+    if (int rc = wide_tab_reserve(h, ntab)) return rc;
     size_t at = 0;
     for (const WideLaunch &l : ls) {
         for (int i = 0; i < count; ++i) {
@@ -3440,46 +3501,234 @@ static int wide_group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPu
         }
     }
     if (at != ntab) return fail(h, WRNN_EINVAL, "wide group: the row tables do not match the plan");
-    // ---- queuing begins
-    HIP_TRY(h, hipMemcpyAsync(h->d_wtab, h->h_wtab, ntab * sizeof(XcdmRow), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipEventRecord(h->ev_wtab, st));
-    HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
-    h->last_path = (int)P_XCDM;
-    // wrnn_elapsed_ms: the loop share of this push (interpolation, draws, resets and persistent
-    // launches of all its rounds), so a caller can split a tick into conditioning and loop
-    HIP_TRY(h, hipEventRecord(h->ev0, st));
     const wrnn_stream *s0 = ss[0];
-    at = 0;
-    for (const WideLaunch &l : ls) {
-        const XcdmRow *tab = h->d_wtab + at;
-        at += (size_t)l.rows;
-        HIP_TRY(h, launch_terms_interp_wide(tab, s0->d_coef, h->d_T, N, s0->hop, s0->nJ, l.rows, l.Lc, st));
-        HIP_TRY(h, launch_draws_wide(h->d_xmnoise, tab, l.rows, l.Lc, K, raw ? 0 : 1, st));
-        // every packed hop element empty, every tag one no step carries (fatchord_xcdm.h)
-        HIP_TRY(h, hipMemsetAsync(h->d_xmxg, 0xFF, (size_t)kXcds * kMXcdStride * 8, st));
-        HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
-        XcdmArgs a{};
-        a.slab = h->d_xmslab;
-        a.terms = h->d_T;
-        a.noise = h->d_xmnoise;
-        a.nz_ts = l.rows;
-        a.nz_t0 = 0;
-        a.nz_b0 = 0;
-        a.xg = h->d_xmxg;
-        a.members = h->d_members;
-        a.ctl = h->d_ctl;
-        a.timeout_ticks = h->timeout_ticks;
-        a.t0 = 0;
-        a.Lc = l.Lc;
-        a.Bt = l.rows;
-        a.nb = l.rows;
-        a.s = h->xms;
-        a.rows = tab;
-        HIP_TRY(h, launch_xcdm_group(a, raw, st));
+    return wide_run_launches(h, ls, ntab, s0->d_coef, s0->hop, s0->nJ, raw, K, st);
+}
+
+// ---- wide lists (wavernn_amd.h: wrnn_list_wide_plan, wrnn_generate_list_wide) ---------------------
+// The one-shot use of the grouped launches: up to kMRowsMax slots, each a queue of whole utterances
+// (list_plan's assignment).  A slot's timeline is its utterances' steps end to end; all rows of a
+// grouped launch run the same number of steps and the kernel takes no per-row mask, so the common
+// timeline is cut at every utterance end on any slot, and again wherever a piece between two such
+// cuts exceeds the steps budget of its row count.  The rows of a launch are the slots whose timeline
+// reaches past its first step, in slot order.
+struct WideListPlan {
+    std::vector<int> slot_of, pos;
+    std::vector<int64_t> slot_frames;
+    std::vector<std::vector<int>> queue;   // [slots]: the slots' utterances in running order
+    std::vector<WideLaunch> ls;            // off: first timeline step
+    long long longest = 0;                 // steps of the longest timeline
+};
+
+static int wide_list_plan(const int *T, int U, int slots, int hop, bool raw, WideListPlan &p, std::string *msg) {
+    p.slot_of.assign(U, 0);
+    p.pos.assign(U, 0);
+    p.slot_frames.assign(slots, 0);
+    p.queue.assign(slots, {});
+    p.ls.clear();
+    list_plan(T, U, slots, p.slot_of.data(), p.pos.data(), p.slot_frames.data(), p.queue.data());
+    std::vector<long long> cuts, ends(slots);
+    p.longest = 0;
+    for (int k = 0; k < slots; ++k) {
+        long long e = 0;
+        for (int u : p.queue[k]) cuts.push_back(e += (long long)T[u] * hop);
+        ends[k] = e;
+        p.longest = std::max(p.longest, e);
     }
-    HIP_TRY(h, hipEventRecord(h->ev1, st));
-    h->timed = true;
+    if (p.longest > INT_MAX) {
+        *msg = "the longest slot timeline exceeds the step counter";
+        return WRNN_EINVAL;
+    }
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    long long prev = 0;
+    for (long long c : cuts) {
+        int rows = 0;
+        for (int k = 0; k < slots; ++k) rows += ends[k] > prev;
+        const int Lc_max = wrnn_wide_steps_per_launch(rows, (int)p.longest, raw ? 1 : 0);
+        if (Lc_max < 1) {
+            *msg = "wrnn_wide_steps_per_launch refused the launch";
+            return WRNN_EINVAL;
+        }
+        for (long long off = prev; off < c; off += Lc_max)
+            p.ls.push_back({(int)off, (int)std::min<long long>(Lc_max, c - off), rows});
+        prev = c;
+    }
     return WRNN_OK;
+}
+
+static int list_wide_args(const int *frames, int U, int slots, int hop, std::string *msg) {
+    if (U < 1) *msg = "a list has at least one utterance";
+    else if (slots < 1 || slots > kMRowsMax) *msg = "slots is 1.." + std::to_string(kMRowsMax) + " (16 per XCD)";
+    else if (hop < 1) *msg = "hop is at least 1";
+    else
+        for (int i = 0; i < U; ++i) {
+            if (frames[i] < 21)
+                *msg = "utterance " + std::to_string(i) + " has " + std::to_string(frames[i]) +
+                       " frames: fewer than 21 (the fade-out, as wrnn_postprocess)";
+            else if ((long long)frames[i] * hop > INT_MAX)
+                *msg = "utterance " + std::to_string(i) + ": hop * frames exceeds the step counter";
+            if (!msg->empty()) break;
+        }
+    return msg->empty() ? WRNN_OK : WRNN_EINVAL;
+}
+
+int wrnn_list_wide_plan(const int *frames, int U, int slots, int hop, int raw, int *slot_of, int *pos_in_slot,
+                        int64_t *slot_frames, int *launch_first, int *launch_steps, int *launch_rows, int cap) {
+    if (!frames) return cond_fail(WRNN_EINVAL, "need frames");
+    std::string msg;
+    if (int rc = list_wide_args(frames, U, slots, hop, &msg)) return cond_fail(rc, msg);
+    WideListPlan p;
+    if (int rc = wide_list_plan(frames, U, slots, hop, raw != 0, p, &msg)) return cond_fail(rc, msg);
+    for (int i = 0; i < U; ++i) {
+        if (slot_of) slot_of[i] = p.slot_of[i];
+        if (pos_in_slot) pos_in_slot[i] = p.pos[i];
+    }
+    for (int k = 0; k < slots; ++k)
+        if (slot_frames) slot_frames[k] = p.slot_frames[k];
+    for (size_t j = 0; j < p.ls.size() && (int)j < cap; ++j) {
+        if (launch_first) launch_first[j] = p.ls[j].off;
+        if (launch_steps) launch_steps[j] = p.ls[j].Lc;
+        if (launch_rows) launch_rows[j] = p.ls[j].rows;
+    }
+    return (int)p.ls.size();
+}
+
+int wrnn_generate_list_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *mel, const float *const *aux,
+                            const int *T, int U, int slots, const float *const *noise, uint64_t seed, int64_t row_offset,
+                            float *const *out, void *stream) {
+    if (!h) return WRNN_EINVAL;
+    if (!h->ready) return fail(h, WRNN_ENOWEIGHTS, "weights not (fully) set");
+    // ---- every argument of every utterance, before anything is queued or any workspace touched
+    if (!ucfg || !mel || !T || !out || U < 1) return fail(h, WRNN_EINVAL, "need ucfg, mel, T, out and U >= 1");
+    if (slots == 0) slots = std::min(kMRowsMax, U);
+    if (h->dm)
+        return fail(h, WRNN_EUNSUPPORTED, "wide lists run the many-row XCD kernel (MoL, or RAW with 9 bits; rnn / fc 512): "
+                                          "this handle is a deepmind one");
+    {
+        const std::string why = wide_refusal(h);
+        if (!why.empty()) return fail(h, WRNN_EUNSUPPORTED, why);
+    }
+    const bool raw = h->cfg.mode == WRNN_MODE_RAW;
+    const int K = raw ? kMRawNC : 11;
+    const int feat = h->cfg.feat_dims, A4 = h->CD - feat;
+    if (ucfg->feat_dims != feat || ucfg->res_out_dims != A4)
+        return fail(h, WRNN_EINVAL, "upsample config does not match the handle's feat / aux dims");
+    if (ucfg->n_scales < 1 || ucfg->n_scales > 4) return fail(h, WRNN_EINVAL, "1..4 upsample scales");
+    for (int i = 0; i < ucfg->n_scales; ++i)
+        if (ucfg->scales[i] < 1 || !ucfg->taps[i]) return fail(h, WRNN_EINVAL, "bad upsample scale / taps");
+    if (A4 > 0 && !aux) return fail(h, WRNN_EINVAL, "need aux (MelResNet outputs)");
+    int hop = 1, nJ = 1, jlo = 0;
+    std::vector<float> coef;
+    if (!frame_weights(*ucfg, &hop, &nJ, &jlo, coef))
+        return fail(h, WRNN_EUNSUPPORTED,
+                    "the upsample cascade has no exact frame-rate form (pad frames < its reach, or more than 8 taps)");
+    std::string msg;
+    if (int rc = list_wide_args(T, U, slots, hop, &msg)) return fail(h, rc, msg);
+    int Tmax = 0;
+    for (int i = 0; i < U; ++i) {
+        if (!mel[i] || !out[i] || (A4 > 0 && !aux[i]) || (noise && !noise[i]))
+            return fail(h, WRNN_EINVAL, "utterance " + std::to_string(i) + ": need mel, aux, out (and its noise)");
+        Tmax = std::max(Tmax, T[i]);
+    }
+    WideListPlan p;
+    if (int rc = wide_list_plan(T, U, slots, hop, raw, p, &msg)) return fail(h, rc, msg);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+
+    // ---- every workspace grown before anything is queued (growing one waits for the device)
+    const int N = kXcdWgs * kMRing;
+    std::vector<size_t> ft_off(U), at_off(U);
+    size_t arena = 0, ntab = 0, t_need = 0, nz_need = 0;
+    for (int i = 0; i < U; ++i) {
+        ft_off[i] = arena;
+        arena += (size_t)(T[i] + nJ - 1) * N;
+        at_off[i] = arena;
+        arena += (size_t)(T[i] + 1) * N;
+    }
+    for (const WideLaunch &l : p.ls) {
+        ntab += (size_t)l.rows;
+        t_need = std::max(t_need, (size_t)(l.Lc + 1) * l.rows * N);   // one row on: the kernel's look-ahead load
+        nz_need = std::max(nz_need, (size_t)(l.Lc + 1) * l.rows * K);
+    }
+    const int fmax = std::max(Tmax + nJ - 1, Tmax + 1);
+    if (grow(h, h->d_frec, h->frec_cap, (size_t)fmax * h->CD) || grow(h, h->d_X, h->X_cap, (size_t)fmax * h->KXc) ||
+        grow(h, h->d_larena, h->larena_cap, arena) || grow(h, h->d_T, h->T_cap, t_need) ||
+        grow(h, h->d_xmnoise, h->xmnoise_cap, nz_need) ||
+        grow(h, h->d_lstate, h->lstate_cap, (size_t)U * kXcdWgs * kMRowStateW))
+        return WRNN_EHIP;
+    if (!h->d_xmxg) HIP_TRY(h, hipMalloc(&h->d_xmxg, (size_t)kXcds * kMXcdStride * 8));
+    if (!h->ev_wtab) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_wtab, hipEventDisableTiming));
+    if (int rc = wide_tab_reserve(h, ntab)) return rc;
+    if (!h->blas && rocblas_create_handle(&h->blas) != rocblas_status_success)
+        return fail(h, WRNN_EHIP, "rocblas_create_handle failed");
+    if (rocblas_set_stream(h->blas, st) != rocblas_status_success) return fail(h, WRNN_EHIP, "rocblas_set_stream failed");
+    if (coef != h->coef_host) {
+        if (grow(h, h->d_coef, h->coef_cap, coef.size())) return WRNN_EHIP;
+        HIP_TRY(h, hipMemcpyAsync(h->d_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipStreamSynchronize(st));   // `coef` is a local: the copy completes before it goes
+        h->coef_host = coef;
+    }
+
+    // ---- the row tables of all launches: a launch lies inside one utterance of every slot it runs,
+    // found by walking each slot's queue along the timeline (cur: the slot's utterance, u0: its first step)
+    std::vector<int> cur(slots, 0);
+    std::vector<long long> u0(slots, 0);
+    size_t at = 0;
+    for (const WideLaunch &l : p.ls) {
+        for (int k = 0; k < slots; ++k) {
+            const std::vector<int> &q = p.queue[k];
+            while (cur[k] < (int)q.size() && u0[k] + (long long)T[q[cur[k]]] * hop <= l.off)
+                u0[k] += (long long)T[q[cur[k]++]] * hop;
+            if (cur[k] >= (int)q.size()) continue;   // the slot's queue has ended: it takes no row
+            const int i = q[cur[k]], t0 = (int)(l.off - u0[k]);
+            if (t0 < 0 || (long long)t0 + l.Lc > (long long)T[i] * hop)
+                return fail(h, WRNN_EINVAL, "wide list: a launch leaves its utterance");
+            XcdmRow r{};
+            r.ft = h->d_larena + ft_off[i];
+            r.at = h->d_larena + at_off[i];
+            r.fr_ld = N;
+            r.noise = noise ? noise[i] + (size_t)t0 * K : nullptr;
+            r.noise_ld = K;
+            r.seed = seed;
+            r.prow = row_offset + i;
+            r.out = out[i] + t0;
+            r.state = h->d_lstate + (size_t)i * kXcdWgs * kMRowStateW;   // the utterance's own record
+            r.ft_base = r.at_base = 0;
+            r.t0 = t0;
+            r.resume = t0 > 0;
+            if (at >= ntab) return fail(h, WRNN_EINVAL, "wide list: the row tables do not match the plan");
+            h->h_wtab[at++] = r;
+        }
+    }
+    if (at != ntab) return fail(h, WRNN_EINVAL, "wide list: the row tables do not match the plan");
+
+    // ---- queuing begins: each utterance's frame terms with the launches and shapes of its own
+    // wrnn_generate_frames call on the many-row path (never one GEMM over several utterances)
+    const float one = 1.0f, zero = 0.0f;
+    XcdmGemm gemms[3];
+    xcdm_terms_gemms(*h, gemms);
+    auto terms_gemm = [&](const float *X, int m, float *C) -> int {
+        for (const XcdmGemm &g : gemms)
+            if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, g.rows, m, g.k, &one,
+                              h->d_xmWt + (size_t)g.row0 * h->KXc + g.col0, h->KXc, X + g.col0, h->KXc, &zero, C + g.row0,
+                              N) != rocblas_status_success)
+                return fail(h, WRNN_EHIP, "rocblas_sgemm (frame terms) failed");
+        return WRNN_OK;
+    };
+    for (int i = 0; i < U; ++i) {
+        FrameSrc fs;
+        fs.mel = mel[i];
+        fs.aux = aux ? aux[i] : nullptr;
+        fs.U = 1;
+        fs.NF = T[i];
+        fs.hop = hop, fs.nJ = nJ, fs.jlo = jlo;
+        fs.coef = h->d_coef;
+        if (int rc = frame_terms(h, fs, N, h->KXc, h->cfg.feat_dims + h->cfg.aux_dims, st, terms_gemm,
+                                 h->d_larena + ft_off[i], h->d_larena + at_off[i]))
+            return rc;
+    }
+    return wide_run_launches(h, p.ls, ntab, h->d_coef, hop, nJ, raw, K, st);
 }
 
 // The group of one, through the launch-wide windowed kernel (wide sessions: the wide group of one)

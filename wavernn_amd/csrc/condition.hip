@@ -257,6 +257,28 @@ hipError_t launch_postprocess_stream(const float *y, int U, int y_ld, int y_t0, 
     return hipGetLastError();
 }
 
+// postprocess_kernel's unbatched case for every utterance of a list in one launch (wrnn_postprocess_list):
+// workgroup (x, y) takes samples [256·x, 256·x + 256) of table entry y — its fp32 loop output, its
+// wave_len and the offset of its float64 waveform in `wave`.  Per sample the operations, their order
+// and the linspace element are postprocess_kernel's (contraction off in both), so the bits are too.
+__global__ void postprocess_list_kernel(const wrnn_post_entry *__restrict__ tab, double *__restrict__ wave, int fade_len,
+                                        double fout_step, int mu_law, double mu) {
+#pragma clang fp contract(off)
+    const wrnn_post_entry e = tab[blockIdx.y];
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= e.wave_len || t >= e.steps) return;
+    double v = (double)e.y[t];
+    if (mu_law) {
+        // np.sign(y) / mu * ((1 + mu) ** np.abs(y) - 1)   (utils/dsp.py:102)
+        const double sg = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
+        v = sg / mu * (pow(mu + 1.0, fabs(v)) - 1.0);
+    }
+    // output[-20·hop:] *= np.linspace(1, 0, 20·hop)   (:255-258)
+    const int q = t - (e.wave_len - fade_len);
+    if (q >= 0) v = v * linspace_at(q, fade_len, 1.0, 0.0, fout_step);
+    wave[e.dst + t] = v;
+}
+
 // ---- content fingerprints (wrnn_fingerprint): one 64-bit sum per tensor, block (chunk, tensor)
 constexpr int kFpMax = 64;        // tensors per launch (the pointer table travels as kernel arguments)
 constexpr int kFpChunks = 32;     // workgroups per tensor
@@ -451,6 +473,21 @@ int wrnn_postprocess(const float *y, int rows, int steps, int batched, int overl
         return cond_fail(WRNN_EINVAL, "wave_len exceeds the generated length");
     }
     hipLaunchKernelGGL(postprocess_kernel, dim3((wave_len + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WRNN_OK : cond_fail(WRNN_EHIP, hipGetErrorString(e));
+}
+
+int wrnn_postprocess_list(const wrnn_post_entry *entries, int U, int max_wave_len, int mu_law, int n_classes,
+                          int fade_len, double *wave, void *stream) {
+    using namespace wrnn;
+    if (!entries || !wave || U < 1 || U > 65535) return cond_fail(WRNN_EINVAL, "need entries, wave and 1..65535 utterances");
+    if (fade_len < 1 || fade_len > max_wave_len)
+        return cond_fail(WRNN_EINVAL, "operands could not be broadcast together: the fade-out (20*hop_length = " +
+                                          std::to_string(fade_len) + ") is longer than the waveform (" +
+                                          std::to_string(max_wave_len) + ")");
+    hipLaunchKernelGGL(postprocess_list_kernel, dim3((max_wave_len + 255) / 256, U), dim3(256), 0, (hipStream_t)stream,
+                       entries, wave, fade_len, (0.0 - 1.0) / (double)(fade_len > 1 ? fade_len - 1 : 1), mu_law != 0 ? 1 : 0,
+                       (double)(n_classes - 1));
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? WRNN_OK : cond_fail(WRNN_EHIP, hipGetErrorString(e));
 }

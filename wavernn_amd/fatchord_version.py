@@ -369,7 +369,8 @@ class WaveRNN(nn.Module):
 
     def generate_list(self, mels: Sequence, save_paths: Optional[Sequence] = None, *, noise=None,
                       seed: Optional[int] = None, row_offset: int = 0, lanes: Optional[int] = None,
-                      verbose: bool = False) -> List[np.ndarray]:
+                      verbose: bool = False, wide: bool = False, slots: Optional[int] = None,
+                      mu_law: bool = True) -> List[np.ndarray]:
         """generate(mels[i], None, False, …) for a list of utterances of ANY lengths (each (1, feat,
         T_i), T_i ≥ 21; unbatched: no folds) in one call: the eight XCDs are eight lanes, each runs
         a queue of utterances back to back inside the persistent launch (longest first, each to the
@@ -383,7 +384,23 @@ class WaveRNN(nn.Module):
         runs per utterance with the shapes of its single call.  `noise`: a sequence of per-utterance
         [hop·T_i][11] draws, indexed by the utterance's own step.  Modes and dims without a list
         kernel (anything but MoL rnn / fc 512 dense or rnn 896 block-sparse: the one-row XCD kernels) raise
-        NotImplementedError; bad arguments raise ValueError before anything is queued."""
+        NotImplementedError; bad arguments raise ValueError before anything is queued.
+
+        Wide lists.  `wide=True` runs the list on the many-row kernel (C-ABI wrnn_generate_list_wide,
+        loop path 7): up to 128 slots, 16 per XCD (`slots` 1..128, default min(128, len(mels));
+        `lanes` must be None), each a queue of utterances that refills when one ends — the form for
+        a batch of hundreds of sentences, and the only list form of a RAW model (9 bits, rnn / fc
+        512; `noise[i]` is then [hop·T_i][512] Exp(1) draws, and `mu_law`, default True as
+        generate_many, expands the samples; it is ignored for MoL).  The post of all utterances is
+        one launch and one copy to the host (wrnn_postprocess_list).  What a wide list promises:
+        utterance i's waveform does not depend on the other utterances, their order, `slots` or
+        WRNN_TERMS_MB — it is bit-identical to the wide list of mels[i] alone with row_offset + i;
+        MoL lies within 2e-5 of the oracle on the same draws and, with `seed`, within MoL tolerance
+        of generate(mels[i], seed=s, row_offset=r + i), but is NOT bit-identical to the narrow list
+        or to generate() (another kernel); RAW class labels are the oracle's and generate()'s on the
+        same draws bit for bit, so with mu_law=False every sample before the fade is exact."""
+        if wide:
+            return self._generate_list_wide(mels, save_paths, noise, seed, row_offset, lanes, slots, mu_law, verbose)
         self.eval()
         start = time.time()
         with torch.no_grad():
@@ -406,6 +423,46 @@ class WaveRNN(nn.Module):
                                       noise=nz, seed=seed, row_offset=row_offset)
             outputs = [condition.postprocess(o[None], False, 0, False, self.n_classes, f[2],
                                              20 * self.hop_length).cpu().numpy() for o, f in zip(outs, fr)]
+        self.last_gen_seconds = time.time() - start
+        if verbose:
+            longest = max(o.shape[0] for o in outs)
+            self.gen_display(longest - 1, longest, len(outs), start)
+        for i, output in enumerate(outputs):
+            if save_paths is not None and save_paths[i] is not None:
+                dsp.save_wav(output, save_paths[i], self.sample_rate)
+        self.train()
+        return outputs
+
+    def _generate_list_wide(self, mels, save_paths, noise, seed, row_offset, lanes, slots, mu_law, verbose):
+        """generate_list(wide=True): every refusal that needs no device work comes before any launch."""
+        if lanes is not None:
+            raise ValueError("lanes belongs to the narrow list: a wide list takes slots (1..128)")
+        if slots is not None and not 1 <= int(slots) <= 128:
+            raise ValueError("slots is 1..128 (16 per XCD)")
+        self.eval()
+        mu_law = mu_law if self.mode == 'RAW' else False
+        start = time.time()
+        with torch.no_grad():
+            ms = self._mel_list(mels)
+            if noise is not None and len(noise) != len(ms):
+                raise ValueError(f"noise holds one [hop·T][{self.noise_width()}] array per utterance")
+            if any(m.shape[2] < 21 for m in ms):   # before the MelResNet launches: nothing is queued
+                raise ValueError("every utterance needs at least 21 frames (the fade-out)")
+            loop = self.loop_handle()
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            dev = ms[0].device
+            nz = None if noise is None else [torch.as_tensor(z, dtype=torch.float32).to(dev).contiguous() for z in noise]
+            if nz is not None:
+                for i, (z, m) in enumerate(zip(nz, ms)):
+                    if tuple(z.shape) != (m.shape[2] * self.hop_length, self.noise_width()):
+                        raise ValueError(f"noise[{i}] must be [{m.shape[2] * self.hop_length}][{self.noise_width()}]")
+            fr = [self.frames(m) for m in ms]   # one MelResNet launch per utterance, at its own shape
+            outs = loop.generate_list_wide(self._upsample_spec(), [f[0] for f in fr], [f[1] for f in fr], slots=slots,
+                                           noise=nz, seed=seed, row_offset=row_offset)
+            wave, off = condition.postprocess_list(outs, [f[2] for f in fr], mu_law, self.n_classes, 20 * self.hop_length)
+            host = wave.cpu().numpy()
+            outputs = [host[o:o + f[2]].copy() for o, f in zip(off, fr)]
         self.last_gen_seconds = time.time() - start
         if verbose:
             longest = max(o.shape[0] for o in outs)

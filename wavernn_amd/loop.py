@@ -360,6 +360,59 @@ class FatchordLoop:
             self.check(stream)
         return outs
 
+    def generate_list_wide(self, spec, mels, auxs, slots: Optional[int] = None, noise=None, seed: int = 0,
+                           row_offset: int = 0, stream=None, check: bool = True) -> list:
+        """generate_list on the many-row kernel (C-ABI wrnn_generate_list_wide): up to 128 slots (16
+        per XCD; `slots` 1..128, default min(128, len(mels))), each running a queue of whole
+        utterances back to back through the grouped launches of wide sessions; MoL and RAW (9 bits).
+        Arguments and result as generate_list; `noise`: per-utterance [hop·T_i][K] draws by the
+        utterance's own step (K = 11 MoL, 512 Exp(1) RAW).  Utterance i's samples do not depend on
+        the other utterances, their order, `slots` or WRNN_TERMS_MB: they are bit-identical to the
+        wide list of utterance i alone with row_offset + i.  MoL: within 2e-5 of the oracle on the
+        same draws (not bit-identical to generate_list / generate_frames: another kernel).  RAW: the
+        class labels are generate()'s on the same draws bit for bit.  Refusals before anything is
+        queued raise ValueError (bad arguments) or NotImplementedError (a loop without the grouped
+        many-row form, with wrnn_stream_open_wide's messages) and leave the handle as it was."""
+        if getattr(self, "_padded", False):
+            raise NotImplementedError("lists need rnn / fc / aux dims that are multiples of 4")
+        U = len(mels)
+        if U < 1 or len(auxs) != U or (noise is not None and len(noise) != U):
+            raise ValueError("mels, auxs (and noise) must be non-empty sequences of one length")
+        if slots is not None and not 1 <= int(slots) <= WIDE_ROWS:
+            raise ValueError(f"slots is 1..{WIDE_ROWS} (16 per XCD), not {slots!r}")
+        for name, ts, C in (("mel", mels, self.feat_dims), ("aux", auxs, 4 * self.aux_dims)):
+            for t in ts:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                        and t.dim() == 3 and t.shape[0] == 1 and t.shape[1] == C):
+                    raise ValueError(f"every {name} must be a contiguous fp32 CUDA tensor [1][{C}][T]")
+        T = [int(m.shape[2]) for m in mels]
+        if any(a.shape[2] != t for a, t in zip(auxs, T)):
+            raise ValueError("an aux has another frame count than its mel")
+        steps, _ = zip(*[spec.shape(1, max(t, 1), 0, 0) for t in T])
+        if noise is not None:
+            for i, z in enumerate(noise):
+                if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()) or \
+                        tuple(z.shape) != (steps[i], self.noise_k):
+                    raise ValueError(f"noise[{i}] must be a contiguous fp32 CUDA tensor [{steps[i]}][{self.noise_k}]")
+        dev = mels[0].device
+        outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in steps]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        vps = ctypes.c_void_p * U
+        rc = nat.lib().wrnn_generate_list_wide(
+            self._h, ctypes.byref(spec.cfg), vps(*[m.data_ptr() for m in mels]), vps(*[a.data_ptr() for a in auxs]),
+            (ctypes.c_int * U)(*T), U, 0 if slots is None else int(slots),
+            vps(*[z.data_ptr() for z in noise]) if noise is not None else None,
+            ctypes.c_uint64(seed & (2 ** 64 - 1)), row_offset, vps(*[o.data_ptr() for o in outs]), stream)
+        if rc == -6:   # WRNN_EUNSUPPORTED
+            raise NotImplementedError((nat.lib().wrnn_last_error(self._h) or b"").decode(errors="replace"))
+        if rc == -1:   # WRNN_EINVAL: nothing was queued
+            raise ValueError((nat.lib().wrnn_last_error(self._h) or b"").decode(errors="replace"))
+        nat.check(self._h, rc)
+        if check:
+            self.check(stream)
+        return outs
+
     def push_streams(self, pushes, stream=None, check: bool = True) -> list:
         """Advance several sessions of this loop in one call (C-ABI wrnn_stream_push_group): `pushes`
         is a sequence of (FatchordStream, mel or None, final), each member with its own frames and
@@ -520,6 +573,32 @@ def list_plan(frames, lanes: Optional[int] = None) -> Tuple[list, list, list]:
     steps = (ctypes.c_int64 * max(int(lanes), 8))()
     nat.check_cond(nat.lib().wrnn_list_plan((ctypes.c_int * n)(*frames), U, int(lanes), lane_of, pos, steps))
     return list(lane_of)[:U], list(pos)[:U], list(steps)[:lanes]
+
+
+def list_wide_plan(frames, slots: Optional[int] = None, hop: int = 275, raw: bool = False) -> Tuple[list, list, list, list]:
+    """The schedule of a wide list call (C-ABI wrnn_list_wide_plan, host only): (slot_of, pos_in_slot,
+    slot_frames, launches) for utterances of `frames` frames on `slots` many-row slots (1..128,
+    default min(128, len(frames))) at `hop` steps per frame.  The assignment is list_plan's rule;
+    `launches` holds one (first timeline step, steps, rows) per persistent launch: the common timeline
+    cut at every utterance end on any slot and again at wide_steps_per_launch(rows, longest timeline,
+    raw) steps, the rows of a launch the slots that still have a step to run, in slot order.  Raises
+    WrnnError(WRNN_EINVAL) for an empty list, slots outside 1..128, hop < 1 or an utterance under 21
+    frames."""
+    frames = [int(f) for f in frames]
+    U = len(frames)
+    if slots is None:
+        slots = min(WIDE_ROWS, max(U, 1))
+    slots = int(slots)
+    n = max(U, 1)
+    slot_of, pos = (ctypes.c_int * n)(), (ctypes.c_int * n)()
+    sf = (ctypes.c_int64 * max(slots, WIDE_ROWS))()
+    args = ((ctypes.c_int * n)(*frames), U, slots, int(hop), int(bool(raw)), slot_of, pos, sf)
+    count = nat.lib().wrnn_list_wide_plan(*args, None, None, None, 0)
+    if count < 0:
+        nat.check_cond(count)
+    first, ls, lr = (ctypes.c_int * count)(), (ctypes.c_int * count)(), (ctypes.c_int * count)()
+    nat.check_cond(min(0, nat.lib().wrnn_list_wide_plan(*args, first, ls, lr, count)))
+    return list(slot_of)[:U], list(pos)[:U], list(sf)[:slots], list(zip(first, ls, lr))
 
 
 def stream_lookahead(spec) -> int:
