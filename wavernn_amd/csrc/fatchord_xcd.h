@@ -14,10 +14,11 @@ constexpr int kXUnits = 16;         // GRU units per workgroup (R / kXcdWgs), 4 
 constexpr int kXFcRows = 16;        // fc1 / fc2 rows per workgroup (F / kXcdWgs)
 // wave roles (all eight compute GRU1, one unit per thread; waves map to SIMD w mod 4):
 //   0, 5..7  GRU2, one wave per SIMD: wave 0 is group g = 0, wave w ≥ 5 group g = w − 4; engine e
-//            of group g owns units 4g + e (lane 0's gates) and 4g + 2 + e (lane 1's), six W_ih2
-//            gate rows in VGPRs, and publishes y, later h2.  Wave 0 also samples (polls F2) and
-//            has W_hh1 rows 0..9; 5..7: W_hh1 rows (5, 7), the h2 gather (6), the ring (7), one
-//            W_hh2 pass in VGPRs + W_hh2 LDS passes (5, 6)
+//            of group g owns units 4g + e (r, z in its lanes 0, 1; n, h' in lane 0) and 4g + 2 + e
+//            (lanes 2, 3; lane 2), six W_ih2 gate rows in VGPRs, and publishes y, later h2 (lanes
+//            0, 2 of engine 0, engine 1's values by a permlane32 swap).  Wave 0 also samples
+//            (polls F2) and has W_hh1 rows 0..9; 5..7: W_hh1 rows (5, 7), the h2 gather (6), the
+//            ring (7), one W_hh2 pass in VGPRs + W_hh2 LDS passes (5, 6)
 //   1, 2     fc1 rows 8h..8h+7 (h = w − 1) from the polled y — polling from barrier B2 on, no
 //            store of their own ahead of the poll; three W_hh2 passes in VGPRs + two from LDS
 //   3, 4     fc2 rows 8h..8h+7 (h = w − 3) from the polled f1 + their fc3 partials; W_hh1 rows

@@ -17,7 +17,8 @@
 // Per step t (x = x_{t-1}):
 //   GRU1 for ALL units, one per thread, from the gathered terms S (rank-1 in x: no hop) → B2
 //   waves 0, 5..7: W_ih2·h1 for the wave's 12 gate rows (VGPR weights, h1 from LDS) → GRU2 gates
-//        (lane 0 / 1 of an engine: its two units) → publish y = x_I + h1 + h2       [hop Y]
+//        (r, z of an engine's two units in its lanes 0..3, the n rows reduced under their sigmoids,
+//        h' in lanes 0 / 2) → publish y = x_I + h1 + h2                              [hop Y]
 //   waves 1, 2 (polling Y from B2 on): fc1 rows (8 per wave) → relu → publish f1  [hop F1]
 //   waves 3, 4: fc2 rows → relu → fc3 partial logits of the workgroup's 16 f2 rows; wave 4 hands
 //        its partials to wave 3 (LDS) → publish 30 partials                        [hop F2]
@@ -59,9 +60,6 @@ namespace wrnn {
 #define WRNN_XCD_SKIP_RECUR 0
 #endif
 #ifndef WRNN_XCD_PRIO
-#ifndef WRNN_XCD_RS
-#define WRNN_XCD_RS 1           // GRU2's three engine dots reduce-scattered (e32dot3_rs; 0: three e32dot, A/B)
-#endif
 #define WRNN_XCD_PRIO 0         // s_setprio of wave 0 (the poller / sampler)
 #endif
 
@@ -143,7 +141,7 @@ namespace wrnn {
         st[tid] = h1v;                                                                                        \
         for (int i = tid; i < 4 * R; i += kXThreads) st[512 + i] = sg[i];                                     \
         if (tid < 48) st[512 + 2048 + tid] = gh2s[tid];                                                       \
-        if (g2w && li < 2) st[512 + 2048 + 48 + ui] = h2own;                                                  \
+        if (g2w && (li & ~2) == 0) st[512 + 2048 + 48 + ui] = h2own;                                          \
         if (tid == 0) st[512 + 2048 + 48 + 16] = xs[(t_end - 1) & 1];                                         \
     } while (0)
 
@@ -312,9 +310,10 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
     auto W4x16 = [&]() -> const f4v(&)[16] { return *reinterpret_cast<const f4v(*)[16]>(&W[0]); };
     // GRU1 of unit tid: x-coefficients
     const float q1r = S[a.s.q1a + tid], q1z = S[a.s.q1a + R + tid], q1n = S[a.s.q1a + 2 * R + tid];
-    // GRU2 waves: the local GRU2 unit whose gates this lane forms (lane 0 / 1 of an engine: its
-    // first / second unit; the other lanes compute along, their results are not used)
-    const int ui = 4 * g2 + 2 * (li & 1) + eng;
+    // GRU2 waves: the local GRU2 unit this lane works for (lanes 0, 1 of an engine: its first unit,
+    // lanes 2, 3: its second; lanes 0 / 2 form r, tanh and h', lanes 1 / 3 z; the other lanes
+    // compute along, their results are not used) and the gate whose sigmoid it forms
+    const int ui = 4 * g2 + (li & 2) + eng, gq = li & 1;
     // W_hh1 rows (waves 0, 3, 4, 5: ten each, wave 7: eight): gh0 + 2p + e, p = 0..4; lane li < 5
     // of an engine publishes the terms of its row gh0 + 2·li + e
     const bool gh1w = wave == 0 || wave == 3 || wave == 4 || wave == 5 || wave == 7;
@@ -406,14 +405,15 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
     };
 
     // a GRU2 wave's four granules of a hop (units 4·g2 .. 4·g2 + 3; unit 4·g2 + 2j + e lives in lane
-    // j of engine e): lanes 0 and 1 store the pairs (lane j, lane 32 + j) as one 16-byte store each,
-    // one instruction, 32 contiguous bytes
-    auto pub4 = [&](int hop, float v, uint32_t tag) {
-        const uint32_t e1a = __builtin_amdgcn_readlane(__float_as_uint(v), 32);
-        const uint32_t e1b = __builtin_amdgcn_readlane(__float_as_uint(v), 33);
-        if (lane < 2)
-            __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(v), tag, lane == 0 ? e1a : e1b, tag}, xgr,
-                                                   (XGI(hop) + c * kXUnits + 4 * g2 + 2 * lane) * 8, 0, 0);
+    // 2j of engine e): lanes 0 and 2 store the pairs (lane 2j, lane 32 + 2j) as one 16-byte store
+    // each, one instruction, 32 contiguous bytes.  Engine 1's value comes by one permlane32 swap
+    // (of v with itself: a lane < 32 finds lane + 32's value in the second result) instead of two
+    // readlanes through SGPRs
+    auto pub4 = [&](int hop, float v, uint32_t tagv) {
+        const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        if ((lane & ~2) == 0)
+            __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(v), tagv, s[1], tagv}, xgr,
+                                                   (XGI(hop) + c * kXUnits + 4 * g2 + lane) * 8, 0, 0);
     };
     // ---- prologue: W_hh1, fc3 columns, small vectors, ring slots t0..t0+2, state
     {
@@ -445,17 +445,19 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
         XSTAMP(0);
         if (kDbg && a.dbg && wave == 0 && lane == 0 && t - t0 < a.dbg_steps)   // shader clock beside the 100 MHz one
             a.dbg[((size_t)mem * a.dbg_steps + (t - t0)) * kStamps + 15] = (unsigned)__builtin_amdgcn_s_memtime();
-        // operands of the GRU2 gate math (this lane's unit ui): LDS reads issued before GRU1's
-        // transcendental chain (behind its h1 store the compiler could not move them).  Every wave
-        // issues them (the fc waves read units 0..3 and drop the values): under a role branch their
-        // waits land at the branch's join, ahead of GRU1, and barrier B2 comes 0.04 µs later
-        float q2v[3], p2v[3], bi2[3], ghv[3];
+        // operands of the GRU2 gate math (this lane's unit ui; [0]: the gate gq whose sigmoid the
+        // lane forms, [1]: the n gate): LDS reads issued before GRU1's transcendental chain (behind
+        // its h1 store the compiler could not move them).  Every wave issues them (the fc waves
+        // read units 0..3 and drop the values): under a role branch their waits land at the
+        // branch's join, ahead of GRU1, and barrier B2 comes 0.04 µs later
+        float q2v[2], p2v[2], bi2[2], ghv[2];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            q2v[q] = cst[XC_Q2 + ui * 3 + q];
-            p2v[q] = tr[XT_P2 + ui * 3 + q];
-            bi2[q] = cst[XC_BIH2 + ui * 3 + q];
-            ghv[q] = gh2s[ui * 3 + q] + cst[XC_BHH2 + ui * 3 + q];
+        for (int q = 0; q < 2; ++q) {
+            const int gi = ui * 3 + (q == 0 ? gq : 2);
+            q2v[q] = cst[XC_Q2 + gi];
+            p2v[q] = tr[XT_P2 + gi];
+            bi2[q] = cst[XC_BIH2 + gi];
+            ghv[q] = gh2s[gi] + cst[XC_BHH2 + gi];
         }
         const float wi0v = cst[XC_WI0 + ui], civ = tr[XT_CI + ui];
         // ---- GRU1 (:208-210), unit tid
@@ -466,42 +468,36 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
             h1v = (h1v - n) * z + n;
             h1s[tid] = h1v;
         }
-        float p2q[3];
+        float p2q[2];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) p2q[q] = fmaf(x, q2v[q], p2v[q]) + bi2[q];
+        for (int q = 0; q < 2; ++q) p2q[q] = fmaf(x, q2v[q], p2v[q]) + bi2[q];
         const float xi = fmaf(wi0v, x, civ);   // x_I of unit ui
         bar();
         XSTAMP(1);
         // ---- GRU2 (:212-214) on waves 0, 5..7: the engine's two units, W_ih2[:, :R]·h1 of their six
-        // gate rows as two 3-row reduce-scatters (each row's sum tree as e32dot's); both leave their
-        // gates in every lane of quad 0, lane 0 takes the first unit's, lane 1 the second's, and one
-        // pass of gate math serves both
+        // gate rows (each row's sum tree as e32dot's).  The four r and z rows first, reduce-scattered
+        // to lanes 0..3 of the engine (a_r, a_z, b_r, b_z), where one sigmoid pass serves all four;
+        // the two n rows and their reduce (a_n → lanes 0, 1, b_n → lanes 2, 3) issue under that
+        // pass's exp → rcp chain.  tanh and h' in lanes 0 and 2: r is the lane's own sigmoid, z its
+        // neighbour's.  Sums and gate math are gru_gate_math's, operation for operation
         if (g2w) {
             f4v hx[4];
             e32x(h1s, li, hx);
             // x_I + h1 of the lane's unit (:212) formed before the dots and pinned there: hipcc
-            // otherwise sinks the h1 LDS read into the publishing lanes' branch after the gate math
+            // otherwise sinks the h1 LDS read into the publishing lanes' branch after the gate math;
+            // the y publish's tag word likewise (a VGPR copy of the step's scalar)
             float yb = xi + h1s[c * kXUnits + ui];
-            asm volatile("" : "+v"(yb));
-            float a_r, a_z, a_n, b_r, b_z, b_n;
-            if (WRNN_XCD_RS) {
-                e32dot3_rs(W4(0), W4(4), W4(8), hx, lane, a_r, a_z, a_n);
-                e32dot3_rs(W4(12), W4(16), W4(20), hx, lane, b_r, b_z, b_n);
-                b_r = WRNN_DPP(b_r, 0x00);   // quad_perm [0,0,0,0]: e32dot3_rs leaves r in lane 0 only
-            } else {
-                a_r = e32dot(W4(0), hx);
-                a_z = e32dot(W4(4), hx);
-                a_n = e32dot(W4(8), hx);
-                b_r = e32dot(W4(12), hx);
-                b_z = e32dot(W4(16), hx);
-                b_n = e32dot(W4(20), hx);
-            }
-            const bool second = (li & 1) != 0;
-            const float g_r = second ? b_r : a_r, g_z = second ? b_z : a_z, g_n = second ? b_n : a_n;
-            const float hn = gru_gate_math(g_r + p2q[0], g_z + p2q[1], g_n + p2q[2], ghv[0], ghv[1], ghv[2], h2own);
+            uint32_t tagv = tag;
+            asm volatile("" : "+v"(yb), "+v"(tagv));
+            const float g_s = e32rs4(e32part(W4(0), hx), e32part(W4(4), hx), e32part(W4(12), hx), e32part(W4(16), hx), lane);
+            const float s = sigmoid_(ghv[0] + (g_s + p2q[0]));   // lane 0: r_a, 1: z_a, 2: r_b, 3: z_b
+            const float g_n = e32rs2(e32part(W4(8), hx), e32part(W4(20), hx), lane);
+            const float z = WRNN_DPP(s, 0xF5);                   // quad_perm [1,1,3,3]
+            const float n = tanh_((g_n + p2q[1]) + ghv[1] * s);
+            const float hn = (h2own - n) * z + n;
             h2own = hn;
             // y = (x_I + h1) + h2 (:212, :216); h2: after hop Y (pub_h2)
-            pub4(XH_Y, yb + hn, tag);
+            pub4(XH_Y, yb + hn, tagv);
             if (wave == 0) set_flag(ypub, tag);
         }
         XSTAMP(2);

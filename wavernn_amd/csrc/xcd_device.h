@@ -193,25 +193,38 @@ __device__ __forceinline__ float e32part(const f4v (&w)[4], const f4v (&x)[4]) {
     return s.x + s.y;
 }
 
-// Three e32dot rows of an engine (the r, z, n gate rows of its unit) reduce-scattered over its 32
-// lanes: lane l keeps row l & 3 (a zero fourth row) against l ^ 1, then l ^ 2, then sums the
-// lanes of its residue class (row_ror 4 and 8, the paired DPP row); lanes 1 and 2 hand z and n
-// to lane 0.  8 cross-lane operations on one chain instead of 3 × 5.  Valid in lanes li == 0.
-__device__ __forceinline__ void e32dot3_rs(const f4v (&w0)[4], const f4v (&w1)[4], const f4v (&w2)[4],
-                                           const f4v (&x)[4], int lane, float &gr, float &gz, float &gn) {
-    const float t0 = e32part(w0, x), t1 = e32part(w1, x), t2 = e32part(w2, x);
+// Σ over the lanes of a residue class (lane & 3) of an engine: the other quads of the DPP row
+// (row_ror 4, then 8), then the paired DPP row.  Read in quad 0 of the engine (lanes li < 4).
+__device__ __forceinline__ float e32rs_tail(float b) {
+    b += WRNN_DPP(b, 0x124);   // row_ror:4
+    b += WRNN_DPP(b, 0x128);   // row_ror:8
+    return perm_sum16(b);
+}
+
+// Four e32part rows of an engine reduce-scattered over its 32 lanes: lane l keeps the rows of
+// its parity against l ^ 1, then row l & 3 against l ^ 2, then e32rs_tail.  Lanes li = 0..3 end
+// with the full sums of rows 0..3 — five cross-lane stages for all four.
+// Every row's sum is the tree pair (l, l ^ 1) → quad → ror 4 → ror 8 → paired DPP row over
+// e32part's in-lane sums, whichever lane of the quad keeps it: each stage adds the same two
+// partial sums (fp32 addition commutes), and the quads meet in quad 0 in the same order.  A row
+// therefore carries the same bits from any residue class, and from e32rs2.
+__device__ __forceinline__ float e32rs4(float t0, float t1, float t2, float t3, int lane) {
     const bool odd = (lane & 1) != 0, hi = (lane & 2) != 0;
     const float u0 = odd ? t1 : t0, v0 = odd ? t0 : t1;
-    const float u1 = odd ? 0.0f : t2, v1 = odd ? t2 : 0.0f;
+    const float u1 = odd ? t3 : t2, v1 = odd ? t2 : t3;
     const float a0 = u0 + WRNN_DPP(v0, 0xB1), a1 = u1 + WRNN_DPP(v1, 0xB1);   // quad_perm [1,0,3,2]
     const float keep = hi ? a1 : a0, send = hi ? a0 : a1;
-    float b = keep + WRNN_DPP(send, 0x4E);                                     // quad_perm [2,3,0,1]
-    b += WRNN_DPP(b, 0x124);                                                   // row_ror:4
-    b += WRNN_DPP(b, 0x128);                                                   // row_ror:8
-    b = perm_sum16(b);
-    gr = b;
-    gz = WRNN_DPP(b, 0x55);   // quad_perm [1,1,1,1]
-    gn = WRNN_DPP(b, 0xAA);   // quad_perm [2,2,2,2]
+    return e32rs_tail(keep + WRNN_DPP(send, 0x4E));                            // quad_perm [2,3,0,1]
+}
+
+// Two rows likewise: a plain add with l ^ 1 (both lanes of a pair hold both pair sums), then
+// lanes with (l & 2) == 0 keep row 0 and the others row 1 against l ^ 2, then e32rs_tail.
+// Lanes li = 0, 1 end with row 0, lanes li = 2, 3 with row 1; the same sum tree as e32rs4.
+__device__ __forceinline__ float e32rs2(float t0, float t1, int lane) {
+    const bool hi = (lane & 2) != 0;
+    const float a0 = t0 + WRNN_DPP(t0, 0xB1), a1 = t1 + WRNN_DPP(t1, 0xB1);   // quad_perm [1,0,3,2]
+    const float keep = hi ? a1 : a0, send = hi ? a0 : a1;
+    return e32rs_tail(keep + WRNN_DPP(send, 0x4E));                            // quad_perm [2,3,0,1]
 }
 
 __device__ __forceinline__ f4v lds4(const float *p) { return *reinterpret_cast<const f4v *>(p); }
