@@ -587,6 +587,80 @@ typedef struct {
 int wrnn_postprocess_list(const wrnn_post_entry *entries, int U, int max_wave_len, int mu_law, int n_classes,
                           int fade_len, double *wave, void *stream);
 
+/* ---- Folded lists: a list of unequal utterances fold-batched on up to 128 many-row slots (additive,
+ * same ABI) ----
+ * The reference's default way to vocode (voc_gen_batched: target 11 000, overlap 550) for a list:
+ * every utterance is cut into folds of Lf = target + 2·overlap steps (fold_with_overlap), and the
+ * folds of ALL utterances are the rows of the grouped many-row launches of wide sessions.  Folds are
+ * all the same length, so the common timeline is cut only at fold boundaries (rounds) and by the
+ * WRNN_TERMS_MB budget; a long utterance spreads over many slots instead of holding one.
+ *
+ * Schedule (wrnn_list_folds_plan; host only, stateless, deterministic).  folds[i] is the row count
+ * wrnn_cond_shape gives for T_i frames (fold_geometry); folds are numbered utterance-major:
+ * first_row[i] = Σ_{j<i} folds[j], F = Σ folds.  Fold g runs in round g / slots as launch row
+ * g % slots (XCD r % 8, slot r / 8 there).  A round is Lf steps of the common timeline, cut into
+ * launches of at most wrnn_wide_steps_per_launch(rows of the round, Lf, raw) steps.
+ *   frames       [U]      frame counts T_i, each >= 21
+ *   hop, target, overlap  steps per frame (>= 1); the fold geometry (target >= 1, overlap >= 0)
+ *   slots                 1..128; 0: min(128, F)
+ *   raw                   0: MoL budget, 1: RAW budget (the 512 draws share it)
+ *   folds, first_row [U]  out (may be NULL, as every output)
+ *   launch_first / launch_steps / launch_rows [cap]  out: per launch its first step on the common
+ *                         timeline (round · Lf + the fold-local step), its steps and its rows
+ * Returns the number of launches; a negative WRNN_EINVAL (message in wrnn_cond_last_error) for
+ * U < 1, slots outside 0..128, hop < 1, target < 1, overlap < 0, any T_i < 21, hop·T_i < overlap
+ * (or an utterance without a fold), or a step or row count past the 32-bit counters.
+ *
+ * wrnn_generate_list_folds: the arguments of wrnn_generate_list_wide with the fold geometry.
+ * out[i] is [folds_i][Lf] fp32 and noise[i], when given, [Lf][folds_i][K] (K = 11 MoL uniforms, 512
+ * Exp(1) draws for RAW) — the layouts wrnn_generate_frames takes for utterance i alone.  It takes
+ * the handles wrnn_generate_list_wide takes and refuses the others with the same texts.  Each
+ * utterance's frame-term stores are computed exactly as the wide list does (never one GEMM over
+ * several utterances); the plan's launches run with the sequence of a wide push, a fold-aware
+ * table-driven interpolation launch in place of the windowed one: launch step j of a fold row is
+ * utterance position p = fold·(target + overlap) + fold-local step; past hop·T_i the terms are
+ * W·[0 | 0 | 1] alone (fold_with_overlap's zero tail).  A fold row is Philox row
+ * row_offset + first_row[i] + fold at its fold-local step — the keys of
+ * wrnn_generate_frames(…, target, overlap, …, row_offset + first_row[i]) of utterance i alone — with
+ * a state record of its own that belongs to this call, zero at the fold's step 0.  Every argument of
+ * every utterance is checked and every workspace grown before anything is queued.  Sets
+ * wrnn_info.last_path to 7 and the timing events as a wide push does.
+ *
+ * What a folded list promises.
+ *   Independence of company: out[i] does not depend on the other utterances, their order, `slots` or
+ *     WRNN_TERMS_MB — it is bit-identical to the folded list of utterance i alone with
+ *     row_offset + first_row[i].
+ *   RAW: out[i] equals the rows of wrnn_generate_frames(target, overlap) of utterance i alone on the
+ *     same draws bit for bit (the labels are exact in both).
+ *   MoL: after wrnn_postprocess_list_folds within √2 · 2·MOL_TOL = 2.83e-5 of the oracle's batched
+ *     generate on the same draws (a sample is the sum of at most two fold samples, each within the
+ *     wide bound 2e-5, with cross-fade weights sqrt(½(1 ± t)) whose sum is <= √2); under Philox within
+ *     √2 · MOL_TOL of the one-shot batched call.  NOT bit-identical to wrnn_generate_frames: another
+ *     instantiation of the kernel. */
+int wrnn_list_folds_plan(const int *frames, int U, int hop, int target, int overlap, int slots, int raw, int *folds,
+                         int *first_row, int *launch_first, int *launch_steps, int *launch_rows, int cap);
+int wrnn_generate_list_folds(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *mel, const float *const *aux,
+                             const int *T, int U, int target, int overlap, int slots, const float *const *noise,
+                             uint64_t seed, int64_t row_offset, float *const *out, void *stream);
+
+/* wrnn_postprocess (batched) for every utterance of a folded list in ONE launch: entry i is
+ * utterance i's fp32 fold output y [rows][steps] (device), its fold count, its wave_len
+ * (fade_len <= wave_len <= rows·(steps − overlap) + overlap) and the offset dst of its float64
+ * waveform in `wave`; `steps` (= target + 2·overlap) and `overlap` are call-wide.  Per utterance:
+ * the optional mu-law expansion, the fade-in / fade-out of each fold, the sum of at most two folds,
+ * the trim to wave_len and the 20-frame fade-out.  wave[dst .. dst + wave_len) equals
+ * wrnn_postprocess(y, rows, steps, 1, overlap, mu_law, n_classes, wave_len, fade_len, …) bit for bit
+ * (with mu-law on: to the accuracy of pow, rtol 1e-12).  `entries` [U] lives in device memory;
+ * max_wave_len >= every wave_len sizes the grid.  WRNN_EINVAL for U outside 1..65535, steps < 1,
+ * fade_len < 1, max_wave_len < fade_len, overlap < 0 or steps − 2·overlap < 1. */
+typedef struct {
+    const float *y;
+    int64_t dst;
+    int32_t rows, wave_len;
+} wrnn_post_fold_entry;
+int wrnn_postprocess_list_folds(const wrnn_post_fold_entry *entries, int U, int steps, int overlap, int max_wave_len,
+                                int mu_law, int n_classes, int fade_len, double *wave, void *stream);
+
 /* Message of the last failed stateless call on this thread. */
 const char *wrnn_cond_last_error(void);
 

@@ -25,6 +25,16 @@ from the first other way that ran is reported.  For (d): the slots, the slot occ
 steps × 11.9 µs, the wide step of DESIGN §4.4c) / loop.  A way the device cannot hold (generate_many
 builds a sample-rate [L_max][rows][208] tensor) is recorded as refused with the error's text; with
 --many-block N, (b) runs the list N utterances at a time, one generate_many after the other.
+--batched: the fold-batched leg instead (target 11 000, overlap 550, the reference's default way to
+vocode), on the list of --utterances, or with --skewed on one 4 800-frame utterance plus 23 of 160:
+  (f) generate_list(list, wide=True, batched=True): all folds on the many-row slots (wrnn_generate_list_folds);
+  (m) generate_many(list, batched=True): all folds as rows, conditioning at sample rate;
+  (s) one generate(batched=True) per utterance;
+  (w) generate_list(list, wide=True): the unbatched wide list.
+For (f): folds, slots, rounds, persistent launches, the slot occupancy folds / (rounds · slots) and the
+loop µs per slot-step (loop / (rounds · 12 100)); for (w) the loop µs per step of the longest slot, the
+same kernel's step in the same process.  (f), (m) and (s) share their Philox keys: the largest
+difference of (f) from the first of (s), (m) that ran is reported (another instantiation: not zero).
 --sparse: the 95 %-pruned rnn-896 model.  --raw: the RAW 9-bit rnn / fc 512 model (mu-law off), which
 has ways (a) and (d) only.  One JSON line per row; --out appends them to a file as well."""
 import argparse
@@ -42,7 +52,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from wavernn_amd import synthetic as syn                     # noqa: E402
 from wavernn_amd.fatchord_version import WaveRNN             # noqa: E402
-from wavernn_amd.loop import list_plan, list_wide_plan       # noqa: E402
+from wavernn_amd.loop import list_folds_plan, list_plan, list_wide_plan   # noqa: E402
 from wavernn_amd.pruning import prune_state                  # noqa: E402
 
 N_XCD = 32 * 160       # terms per row and step of the one-row XCD kernel (csrc/fatchord_xcd.h)
@@ -196,6 +206,102 @@ def run_case(model, d, mels, ways, reps, dev, what, emit, many_block=0):
         emit(row)
 
 
+def run_batched(model, d, mels, ways, reps, dev, what, emit, target=11000, overlap=550):
+    """The fold-batched leg: ways f, m, s, w of the module docstring on one list."""
+    frames = [int(m.shape[2]) for m in mels]
+    hop, U = d.hop_length, len(mels)
+    samples = sum((T - 1) * hop for T in frames)
+    loop = model.loop_handle()
+    seed = 1000
+    raw = d.mode == "RAW"
+    Lf = target + 2 * overlap
+    folds, first, launches = list_folds_plan(frames, hop, target, overlap, raw=raw)
+    F = sum(folds)
+    slots = min(128, F)
+    rounds = -(-F // slots)
+
+    def folded():
+        out = model.generate_list(mels, seed=seed, wide=True, batched=True, target=target, overlap=overlap, mu_law=False)
+        return out, loop.elapsed_ms()
+
+    def many():
+        out = model.generate_many(mels, None, True, target, overlap, False, seed=seed)
+        return out, loop.elapsed_ms()
+
+    def single():
+        out, ms = [], 0.0
+        for i, m in enumerate(mels):
+            out.append(model.generate(m, None, True, target, overlap, False, seed=seed, row_offset=first[i], verbose=False))
+            ms += loop.elapsed_ms()
+        return out, ms
+
+    def wide():
+        out = model.generate_list(mels, seed=seed, wide=True, mu_law=False)
+        return out, loop.elapsed_ms()
+
+    fns = {"f": ("generate_list(wide=True, batched=True)", folded), "m": ("generate_many(batched=True)", many),
+           "s": ("one generate(batched=True) per utterance", single), "w": ("generate_list(wide=True)", wide)}
+    audio, wall, dev_ms, refused = {}, {w: [] for w in ways}, {w: [] for w in ways}, {}
+    for rep_i in range(reps + 1):        # rep 0: the untimed warm-up of every shape
+        for w in ways:
+            if w in refused:
+                continue
+            try:
+                (out, lms), ms = _wall(fns[w][1], dev)
+            except (NotImplementedError, torch.cuda.OutOfMemoryError) as e:
+                refused[w] = f"{type(e).__name__}: {e}".splitlines()[0]
+                torch.cuda.empty_cache()
+                continue
+            audio[w] = out
+            if rep_i:
+                wall[w].append(ms)
+                dev_ms[w].append(lms)
+    other = next((w for w in ("s", "m") if w in audio), None)
+    delta, parted = None, []
+    if "f" in audio and other:
+        delta = max(float(np.abs(x - y).max()) for x, y in zip(audio["f"], audio[other]))
+        # utterances where the two kernels' samplers took different branches (a near-tie in the mixture
+        # selection): where they part, and whether the folded result is still its own list of one
+        for i, (x, y) in enumerate(zip(audio["f"], audio[other])):
+            far = np.flatnonzero(np.abs(x - y) > 1e-5)
+            if far.size:
+                alone = model.generate_list([mels[i]], seed=seed, row_offset=first[i], wide=True, batched=True, target=target,
+                                            overlap=overlap, mu_law=False)[0]
+                parted.append({"utterance": i, "frames": frames[i], "max_abs_diff": float(np.abs(x - y).max()),
+                               "first_sample_beyond_1e-5": int(far[0]),
+                               "max_abs_diff_before_it": float(np.abs(x - y)[:far[0]].max()) if far[0] else 0.0,
+                               "equal_to_its_folded_list_of_one": bool(np.array_equal(alone, x))})
+    for w in ways:
+        row = {"what": what, "way": fns[w][0], "utterances": U, "frames_min_max": [min(frames), max(frames)],
+               "target_overlap": [target, overlap], "folds": F, "reps": reps}
+        if w in refused:
+            row["refused"] = refused[w]
+            emit(row)
+            continue
+        med, loop_ms = statistics.median(wall[w]), statistics.median(dev_ms[w])
+        row.update({"wall_ms": round(med, 2), "wall_ms_min_max": [round(min(wall[w]), 2), round(max(wall[w]), 2)],
+                    "samples_per_s": round(samples / med * 1e3), "x_real_time": round(samples / d.sample_rate / med * 1e3, 2),
+                    "loop_device_ms": round(loop_ms, 2),
+                    "loop_device_ms_min_max": [round(min(dev_ms[w]), 2), round(max(dev_ms[w]), 2)],
+                    "outside_loop_ms": round(med - loop_ms, 2)})
+        if w == "f":
+            assert sum(s for _, s, _ in launches) == rounds * Lf
+            row.update({"slots": slots, "rounds": rounds, "persistent_launches": len(launches),
+                        "slot_occupancy": round(F / (rounds * slots), 4), "slot_steps": rounds * Lf,
+                        "loop_us_per_slot_step": round(loop_ms * 1e3 / (rounds * Lf), 4),
+                        "max_abs_diff_from": {"way": fns[other][0], "value": delta} if other else None,
+                        "utterances_beyond_1e-5": parted})
+        elif w == "w":
+            _, _, slot_frames, ls = list_wide_plan(frames, None, hop=hop, raw=raw)
+            longest = max(slot_frames) * hop
+            row.update({"slots": len(slot_frames), "persistent_launches": len(ls), "longest_slot_steps": longest,
+                        "slot_occupancy": round(sum(T * hop for T in frames) / (len(slot_frames) * longest), 4),
+                        "loop_us_per_step_of_the_longest_slot": round(loop_ms * 1e3 / longest, 4)})
+        elif w == "m":
+            row["row_steps_run"] = F * Lf
+        emit(row)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=3)
@@ -206,6 +312,8 @@ def main():
     ap.add_argument("--many-block", type=int, default=0, help="(b) in blocks of this many utterances")
     ap.add_argument("--skip-equal", action="store_true", help="leave out the eight equal utterances")
     ap.add_argument("--skip-single", action="store_true", help="leave out (a), the slowest way")
+    ap.add_argument("--batched", action="store_true", help="the fold-batched leg (ways fmsw; target 11000, overlap 550)")
+    ap.add_argument("--skewed", action="store_true", help="--batched: one 4800-frame utterance plus 23 of 160 frames")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -230,6 +338,16 @@ def main():
     lengths = [401 if U == 1 else 101 + round(i * 300 / (U - 1)) for i in range(U)]
     np.random.default_rng(24).shuffle(lengths)       # arrival order, not sorted
     mixed = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=10 + i))[None].to(dev) for i, T in enumerate(lengths)]
+    if args.batched:
+        ways = tuple(args.ways) if args.ways else ("f", "m", "s", "w")
+        if args.skewed:
+            sk = [4800] + [160] * 23
+            mels = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=300 + i))[None].to(dev) for i, T in enumerate(sk)]
+            run_batched(model, d, mels, ways, args.reps, dev, "skewed list, one of 4800 frames and 23 of 160", emit)
+        else:
+            run_batched(model, d, mixed, ways, args.reps, dev, f"mixed list, {min(lengths)}..{max(lengths)} frames", emit)
+        model.train()
+        return
     ways = tuple(args.ways) if args.ways else ("a", "d") if args.raw else ("a", "b", "c") if args.sparse else ("a", "b", "c", "d")
     if args.skip_single:
         ways = tuple(w for w in ways if w != "a")

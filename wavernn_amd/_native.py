@@ -24,7 +24,7 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint",
            "wrnn_list_plan", "wrnn_generate_list", "wrnn_stream_open_wide", "wrnn_wide_plan",
            "wrnn_stream_mu_law", "wrnn_wide_steps_per_launch", "wrnn_list_wide_plan", "wrnn_generate_list_wide",
-           "wrnn_postprocess_list")
+           "wrnn_postprocess_list", "wrnn_list_folds_plan", "wrnn_generate_list_folds", "wrnn_postprocess_list_folds")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -155,6 +155,16 @@ def lib() -> ctypes.CDLL:
     # entries [U] (device), U, max_wave_len, mu_law, n_classes, fade_len, wave (device), stream
     L.wrnn_postprocess_list.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
     L.wrnn_postprocess_list.restype = i32
+    # frames [U], U, hop, target, overlap, slots, raw → folds [U], first_row [U], launch_first / steps / rows [cap], cap
+    L.wrnn_list_folds_plan.argtypes = [pi, i32, i32, i32, i32, i32, i32, pi, pi, pi, pi, pi, i32]
+    L.wrnn_list_folds_plan.restype = i32
+    # wrnn_generate_list_wide's arguments with (target, overlap) before slots
+    L.wrnn_generate_list_folds.argtypes = [vp, ctypes.POINTER(UpsampleCfg), ctypes.POINTER(vp), ctypes.POINTER(vp), pi, i32,
+                                           i32, i32, i32, ctypes.POINTER(vp), u64, i64, ctypes.POINTER(vp), vp]
+    L.wrnn_generate_list_folds.restype = i32
+    # entries [U] (device), U, steps, overlap, max_wave_len, mu_law, n_classes, fade_len, wave (device), stream
+    L.wrnn_postprocess_list_folds.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.wrnn_postprocess_list_folds.restype = i32
     L.wrnn_fingerprint.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i64), i32, vp, vp]
     L.wrnn_fingerprint.restype = i32
     L.wrnn_cond_last_error.argtypes = []

@@ -11,7 +11,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "_lib", "libwavernn_amd.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("fatchord_loop.hip", "fatchord_split.hip", "fatchord_xcd.hip", "fatchord_xcds.hip", "fatchord_xcdm.hip", "fatchord_rows.hip", "deepmind_rows.hip", "deepmind_xcd.hip", "condition.hip", "frame_terms.hip", "melresnet.hip", "capi.cpp")]
-HEADERS = [os.path.join(CSRC, f) for f in ("fatchord_loop.h", "fatchord_split.h", "fatchord_xcd.h", "fatchord_xcds.h", "fatchord_xcdm.h", "deepmind_xcd.h", "mfma_device.h", "xcd_device.h", "fatchord_rows.h", "deepmind_rows.h", "wrnn_device.h",
+HEADERS = [os.path.join(CSRC, f) for f in ("fatchord_loop.h", "fatchord_split.h", "fatchord_xcd.h", "fatchord_xcds.h", "fatchord_xcdm.h", "deepmind_xcd.h", "mfma_device.h", "xcd_device.h", "fatchord_rows.h", "deepmind_rows.h", "wrnn_device.h", "frame_terms.h",
                                            "rows_device.h")] + \
     [os.path.join(REPO, "include", "wavernn_amd.h")]
 ARCH = os.environ.get("WRNN_OFFLOAD_ARCH", "gfx950")

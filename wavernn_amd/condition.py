@@ -198,3 +198,42 @@ def postprocess_list(ys, wave_lens, mu_law: bool, n_classes: int, fade_len: int)
     nat.check_cond(nat.lib().wrnn_postprocess_list(d_tab.data_ptr(), len(ys), max(wave_lens), int(mu_law), n_classes,
                                                    fade_len, wave.data_ptr(), _stream(dev)))
     return wave, off
+
+
+POST_FOLD_ENTRY = np.dtype([("y", np.uint64), ("dst", np.int64), ("rows", np.int32), ("wave_len", np.int32)])
+
+
+def postprocess_list_folds(ys, overlap: int, wave_lens, mu_law: bool, n_classes: int,
+                           fade_len: int) -> Tuple[torch.Tensor, list]:
+    """The batched postprocess of every utterance of a folded list in one launch (C-ABI
+    wrnn_postprocess_list_folds): ys[i] [folds_i][steps] fp32 fold outputs on the GPU (one `steps` =
+    target + 2·overlap for all), wave_lens[i] its waveform length → (one float64 device buffer, the
+    utterances' offsets in it): utterance i's waveform is buffer[off_i : off_i + wave_lens[i]], what
+    postprocess(ys[i], True, overlap, mu_law, n_classes, wave_lens[i], fade_len) gives (bit for bit;
+    with mu-law on to pow's accuracy)."""
+    ys = [y.contiguous().float() for y in ys]
+    _need_gpu(*ys)
+    wave_lens = [int(w) for w in wave_lens]
+    if not ys or len(ys) != len(wave_lens):
+        raise ValueError("ys and wave_lens hold one entry per utterance, at least one")
+    if any(y.dim() != 2 or y.shape[0] < 1 for y in ys) or len({y.shape[1] for y in ys}) != 1:
+        raise ValueError("every ys[i] must be a [folds][steps] tensor, one steps for all")
+    steps, overlap = int(ys[0].shape[1]), int(overlap)
+    if overlap < 0 or steps - 2 * overlap < 1:
+        raise ValueError(f"bad overlap {overlap} for the fold length {steps}")
+    tab = np.zeros(len(ys), POST_FOLD_ENTRY)
+    off, total = [], 0
+    for i, (y, w) in enumerate(zip(ys, wave_lens)):
+        if w > y.shape[0] * (steps - overlap) + overlap:
+            raise ValueError(f"wave_lens[{i}] = {w} exceeds the unfolded length of ys[{i}]")
+        if fade_len > w:
+            raise ValueError(f"operands could not be broadcast together with shapes ({w},) ({fade_len},) ")
+        tab[i] = (y.data_ptr(), total, y.shape[0], w)
+        off.append(total)
+        total += w
+    dev = ys[0].device
+    d_tab = torch.from_numpy(tab.view(np.uint8)).to(dev)
+    wave = torch.empty(total, device=dev, dtype=torch.float64)
+    nat.check_cond(nat.lib().wrnn_postprocess_list_folds(d_tab.data_ptr(), len(ys), steps, overlap, max(wave_lens),
+                                                         int(mu_law), n_classes, fade_len, wave.data_ptr(), _stream(dev)))
+    return wave, off

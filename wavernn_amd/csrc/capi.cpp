@@ -26,6 +26,7 @@
 #include "fatchord_xcds.h"
 #include "fatchord_xcdm.h"
 #include "deepmind_xcd.h"
+#include "frame_terms.h"
 
 namespace wrnn {
 hipError_t launch_ci_gemm(const float *cond, int CD, int Bt, int b0, int Bc, int t0, int L, const float *W, int ldw,
@@ -76,6 +77,8 @@ hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool raw, bool *ok);
 hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, int K, int mol, hipStream_t st);
 hipError_t launch_terms_interp_wide(const XcdmRow *rows, const float *coef, float *T, int N, int hop, int nJ, int nb,
                                     int nt, hipStream_t st);
+hipError_t launch_terms_interp_folds(const XcdmRow *rows, const FoldRow *folds, const float *coef, float *T, int N,
+                                     int hop, int nJ, int nb, int nt, hipStream_t st);
 hipError_t launch_dx(const DxArgs &a, hipStream_t st);
 hipError_t prepare_dx_kernel(int max_lds_bytes, bool *ok);
 int cond_fail(int code, const std::string &m);
@@ -3382,6 +3385,10 @@ int wrnn_wide_plan(const int *steps, const int *rows, int count, int steps_per_l
     return (int)ls.size();
 }
 
+// Row-table records that hold the `ntab` fold records of a folded list (frame_terms.h: FoldRow): they
+// ride behind the row records in the same table, so one upload brings both
+static size_t fold_tab_records(size_t ntab) { return (ntab * sizeof(FoldRow) + sizeof(XcdmRow) - 1) / sizeof(XcdmRow); }
+
 // The device row table and its pinned staging copy, sized for `ntab` records; returns once the last
 // upload has read the staging copy, so the caller may rewrite it.
 static int wide_tab_reserve(wrnn_t *h, size_t ntab) {
@@ -3401,12 +3408,16 @@ static int wide_tab_reserve(wrnn_t *h, size_t ntab) {
 // The launch loop of a wide push and of a wide list: the `ntab` records of h_wtab (the launches' row
 // tables one after the other) go up once, then per launch one interpolation launch into the shared
 // terms, one draws launch, the hop area reset, the member counters and one persistent launch.  The
-// workspaces are grown already; nothing here waits on the stream.
+// workspaces are grown already; nothing here waits on the stream.  `folds`: the rows are folds of a
+// folded list — the table holds fold_tab_records(ntab) more records, the FoldRow of every row in
+// table order, and the fold-aware interpolation takes the place of the windowed one.
 static int wide_run_launches(wrnn_t *h, const std::vector<WideLaunch> &ls, size_t ntab, const float *d_coef, int hop,
-                             int nJ, bool raw, int K, hipStream_t st) {
+                             int nJ, bool raw, int K, hipStream_t st, bool folds = false) {
     const int N = kXcdWgs * kMRing;
+    const size_t nup = ntab + (folds ? fold_tab_records(ntab) : 0);
+    const FoldRow *d_folds = reinterpret_cast<const FoldRow *>(h->d_wtab + ntab);
     // ---- queuing begins
-    HIP_TRY(h, hipMemcpyAsync(h->d_wtab, h->h_wtab, ntab * sizeof(XcdmRow), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(h->d_wtab, h->h_wtab, nup * sizeof(XcdmRow), hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipEventRecord(h->ev_wtab, st));
     HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
     h->last_path = (int)P_XCDM;
@@ -3416,8 +3427,9 @@ static int wide_run_launches(wrnn_t *h, const std::vector<WideLaunch> &ls, size_
     size_t at = 0;
     for (const WideLaunch &l : ls) {
         const XcdmRow *tab = h->d_wtab + at;
+        if (folds) HIP_TRY(h, launch_terms_interp_folds(tab, d_folds + at, d_coef, h->d_T, N, hop, nJ, l.rows, l.Lc, st));
+        else HIP_TRY(h, launch_terms_interp_wide(tab, d_coef, h->d_T, N, hop, nJ, l.rows, l.Lc, st));
         at += (size_t)l.rows;
-        HIP_TRY(h, launch_terms_interp_wide(tab, d_coef, h->d_T, N, hop, nJ, l.rows, l.Lc, st));
         HIP_TRY(h, launch_draws_wide(h->d_xmnoise, tab, l.rows, l.Lc, K, raw ? 0 : 1, st));
         // every packed hop element empty, every tag one no step carries (fatchord_xcdm.h)
         HIP_TRY(h, hipMemsetAsync(h->d_xmxg, 0xFF, (size_t)kXcds * kMXcdStride * 8, st));
@@ -3594,6 +3606,80 @@ int wrnn_list_wide_plan(const int *frames, int U, int slots, int hop, int raw, i
     return (int)p.ls.size();
 }
 
+// The checks a wide list and a folded list share, before anything is queued or any workspace touched:
+// the handle has the grouped many-row form, the upsample config matches it and has an exact
+// frame-rate form → hop, nJ, jlo and the frame weights.
+static int wide_list_handle_args(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *aux, int *hop_out,
+                                 int *nJ_out, int *jlo_out, std::vector<float> &coef) {
+    if (h->dm)
+        return fail(h, WRNN_EUNSUPPORTED, "wide lists run the many-row XCD kernel (MoL, or RAW with 9 bits; rnn / fc 512): "
+                                          "this handle is a deepmind one");
+    {
+        const std::string why = wide_refusal(h);
+        if (!why.empty()) return fail(h, WRNN_EUNSUPPORTED, why);
+    }
+    const int feat = h->cfg.feat_dims, A4 = h->CD - feat;
+    if (ucfg->feat_dims != feat || ucfg->res_out_dims != A4)
+        return fail(h, WRNN_EINVAL, "upsample config does not match the handle's feat / aux dims");
+    if (ucfg->n_scales < 1 || ucfg->n_scales > 4) return fail(h, WRNN_EINVAL, "1..4 upsample scales");
+    for (int i = 0; i < ucfg->n_scales; ++i)
+        if (ucfg->scales[i] < 1 || !ucfg->taps[i]) return fail(h, WRNN_EINVAL, "bad upsample scale / taps");
+    if (A4 > 0 && !aux) return fail(h, WRNN_EINVAL, "need aux (MelResNet outputs)");
+    if (!frame_weights(*ucfg, hop_out, nJ_out, jlo_out, coef))
+        return fail(h, WRNN_EUNSUPPORTED,
+                    "the upsample cascade has no exact frame-rate form (pad frames < its reach, or more than 8 taps)");
+    return WRNN_OK;
+}
+
+// The handle-side preparations they share, after the checks and before the row tables: the hop area,
+// the upload event, rocBLAS on the stream and the frame weights on the device.
+static int wide_list_prepare(wrnn_t *h, const std::vector<float> &coef, hipStream_t st) {
+    if (!h->d_xmxg) HIP_TRY(h, hipMalloc(&h->d_xmxg, (size_t)kXcds * kMXcdStride * 8));
+    if (!h->ev_wtab) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_wtab, hipEventDisableTiming));
+    if (!h->blas && rocblas_create_handle(&h->blas) != rocblas_status_success)
+        return fail(h, WRNN_EHIP, "rocblas_create_handle failed");
+    if (rocblas_set_stream(h->blas, st) != rocblas_status_success) return fail(h, WRNN_EHIP, "rocblas_set_stream failed");
+    if (coef != h->coef_host) {
+        if (grow(h, h->d_coef, h->coef_cap, coef.size())) return WRNN_EHIP;
+        HIP_TRY(h, hipMemcpyAsync(h->d_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipStreamSynchronize(st));   // the caller's `coef` may be a local: the copy completes before it goes
+        h->coef_host = coef;
+    }
+    return WRNN_OK;
+}
+
+// Each utterance's frame-term stores in the list arena, with the launches and shapes of its own
+// wrnn_generate_frames call on the many-row path (never one GEMM over several utterances)
+static int wide_list_frame_terms(wrnn_t *h, const float *const *mel, const float *const *aux, const int *T, int U, int hop,
+                                 int nJ, int jlo, const std::vector<size_t> &ft_off, const std::vector<size_t> &at_off,
+                                 hipStream_t st) {
+    const int N = kXcdWgs * kMRing;
+    const float one = 1.0f, zero = 0.0f;
+    XcdmGemm gemms[3];
+    xcdm_terms_gemms(*h, gemms);
+    auto terms_gemm = [&](const float *X, int m, float *C) -> int {
+        for (const XcdmGemm &g : gemms)
+            if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, g.rows, m, g.k, &one,
+                              h->d_xmWt + (size_t)g.row0 * h->KXc + g.col0, h->KXc, X + g.col0, h->KXc, &zero, C + g.row0,
+                              N) != rocblas_status_success)
+                return fail(h, WRNN_EHIP, "rocblas_sgemm (frame terms) failed");
+        return WRNN_OK;
+    };
+    for (int i = 0; i < U; ++i) {
+        FrameSrc fs;
+        fs.mel = mel[i];
+        fs.aux = aux ? aux[i] : nullptr;
+        fs.U = 1;
+        fs.NF = T[i];
+        fs.hop = hop, fs.nJ = nJ, fs.jlo = jlo;
+        fs.coef = h->d_coef;
+        if (int rc = frame_terms(h, fs, N, h->KXc, h->cfg.feat_dims + h->cfg.aux_dims, st, terms_gemm,
+                                 h->d_larena + ft_off[i], h->d_larena + at_off[i]))
+            return rc;
+    }
+    return WRNN_OK;
+}
+
 int wrnn_generate_list_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *mel, const float *const *aux,
                             const int *T, int U, int slots, const float *const *noise, uint64_t seed, int64_t row_offset,
                             float *const *out, void *stream) {
@@ -3602,27 +3688,12 @@ int wrnn_generate_list_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const floa
     // ---- every argument of every utterance, before anything is queued or any workspace touched
     if (!ucfg || !mel || !T || !out || U < 1) return fail(h, WRNN_EINVAL, "need ucfg, mel, T, out and U >= 1");
     if (slots == 0) slots = std::min(kMRowsMax, U);
-    if (h->dm)
-        return fail(h, WRNN_EUNSUPPORTED, "wide lists run the many-row XCD kernel (MoL, or RAW with 9 bits; rnn / fc 512): "
-                                          "this handle is a deepmind one");
-    {
-        const std::string why = wide_refusal(h);
-        if (!why.empty()) return fail(h, WRNN_EUNSUPPORTED, why);
-    }
-    const bool raw = h->cfg.mode == WRNN_MODE_RAW;
-    const int K = raw ? kMRawNC : 11;
-    const int feat = h->cfg.feat_dims, A4 = h->CD - feat;
-    if (ucfg->feat_dims != feat || ucfg->res_out_dims != A4)
-        return fail(h, WRNN_EINVAL, "upsample config does not match the handle's feat / aux dims");
-    if (ucfg->n_scales < 1 || ucfg->n_scales > 4) return fail(h, WRNN_EINVAL, "1..4 upsample scales");
-    for (int i = 0; i < ucfg->n_scales; ++i)
-        if (ucfg->scales[i] < 1 || !ucfg->taps[i]) return fail(h, WRNN_EINVAL, "bad upsample scale / taps");
-    if (A4 > 0 && !aux) return fail(h, WRNN_EINVAL, "need aux (MelResNet outputs)");
     int hop = 1, nJ = 1, jlo = 0;
     std::vector<float> coef;
-    if (!frame_weights(*ucfg, &hop, &nJ, &jlo, coef))
-        return fail(h, WRNN_EUNSUPPORTED,
-                    "the upsample cascade has no exact frame-rate form (pad frames < its reach, or more than 8 taps)");
+    if (int rc = wide_list_handle_args(h, ucfg, aux, &hop, &nJ, &jlo, coef)) return rc;
+    const bool raw = h->cfg.mode == WRNN_MODE_RAW;
+    const int K = raw ? kMRawNC : 11;
+    const int A4 = h->CD - h->cfg.feat_dims;
     std::string msg;
     if (int rc = list_wide_args(T, U, slots, hop, &msg)) return fail(h, rc, msg);
     int Tmax = 0;
@@ -3657,18 +3728,8 @@ int wrnn_generate_list_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const floa
         grow(h, h->d_xmnoise, h->xmnoise_cap, nz_need) ||
         grow(h, h->d_lstate, h->lstate_cap, (size_t)U * kXcdWgs * kMRowStateW))
         return WRNN_EHIP;
-    if (!h->d_xmxg) HIP_TRY(h, hipMalloc(&h->d_xmxg, (size_t)kXcds * kMXcdStride * 8));
-    if (!h->ev_wtab) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_wtab, hipEventDisableTiming));
+    if (int rc = wide_list_prepare(h, coef, st)) return rc;
     if (int rc = wide_tab_reserve(h, ntab)) return rc;
-    if (!h->blas && rocblas_create_handle(&h->blas) != rocblas_status_success)
-        return fail(h, WRNN_EHIP, "rocblas_create_handle failed");
-    if (rocblas_set_stream(h->blas, st) != rocblas_status_success) return fail(h, WRNN_EHIP, "rocblas_set_stream failed");
-    if (coef != h->coef_host) {
-        if (grow(h, h->d_coef, h->coef_cap, coef.size())) return WRNN_EHIP;
-        HIP_TRY(h, hipMemcpyAsync(h->d_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipStreamSynchronize(st));   // `coef` is a local: the copy completes before it goes
-        h->coef_host = coef;
-    }
 
     // ---- the row tables of all launches: a launch lies inside one utterance of every slot it runs,
     // found by walking each slot's queue along the timeline (cur: the slot's utterance, u0: its first step)
@@ -3703,32 +3764,182 @@ int wrnn_generate_list_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const floa
     }
     if (at != ntab) return fail(h, WRNN_EINVAL, "wide list: the row tables do not match the plan");
 
-    // ---- queuing begins: each utterance's frame terms with the launches and shapes of its own
-    // wrnn_generate_frames call on the many-row path (never one GEMM over several utterances)
-    const float one = 1.0f, zero = 0.0f;
-    XcdmGemm gemms[3];
-    xcdm_terms_gemms(*h, gemms);
-    auto terms_gemm = [&](const float *X, int m, float *C) -> int {
-        for (const XcdmGemm &g : gemms)
-            if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, g.rows, m, g.k, &one,
-                              h->d_xmWt + (size_t)g.row0 * h->KXc + g.col0, h->KXc, X + g.col0, h->KXc, &zero, C + g.row0,
-                              N) != rocblas_status_success)
-                return fail(h, WRNN_EHIP, "rocblas_sgemm (frame terms) failed");
-        return WRNN_OK;
-    };
-    for (int i = 0; i < U; ++i) {
-        FrameSrc fs;
-        fs.mel = mel[i];
-        fs.aux = aux ? aux[i] : nullptr;
-        fs.U = 1;
-        fs.NF = T[i];
-        fs.hop = hop, fs.nJ = nJ, fs.jlo = jlo;
-        fs.coef = h->d_coef;
-        if (int rc = frame_terms(h, fs, N, h->KXc, h->cfg.feat_dims + h->cfg.aux_dims, st, terms_gemm,
-                                 h->d_larena + ft_off[i], h->d_larena + at_off[i]))
-            return rc;
-    }
+    // ---- queuing begins
+    if (int rc = wide_list_frame_terms(h, mel, aux, T, U, hop, nJ, jlo, ft_off, at_off, st)) return rc;
     return wide_run_launches(h, p.ls, ntab, h->d_coef, hop, nJ, raw, K, st);
+}
+
+// ---- folded lists (wavernn_amd.h: wrnn_list_folds_plan, wrnn_generate_list_folds) ------------------
+// The folds of all utterances, numbered utterance-major, are the rows: fold g runs in round g / slots
+// as launch row g % slots.  Folds are all Lf = target + 2·overlap steps, so the common timeline is cut
+// at round ends only, and again wherever a round exceeds the steps budget of its row count.
+struct FoldListPlan {
+    std::vector<int> folds, first_row;
+    int F = 0, slots = 0, Lf = 0;
+    std::vector<WideLaunch> ls;   // off: first fold-local step (the launches of round q follow those of round q − 1)
+    std::vector<int> round_of;    // [launches]
+};
+
+static int fold_list_plan(const int *frames, int U, int hop, int target, int overlap, int slots, bool raw, FoldListPlan &p,
+                          std::string *msg) {
+    if (U < 1) *msg = "a list has at least one utterance";
+    else if (slots < 0 || slots > kMRowsMax) *msg = "slots is 1.." + std::to_string(kMRowsMax) + " (16 per XCD), or 0 for min(" + std::to_string(kMRowsMax) + ", folds)";
+    else if (hop < 1) *msg = "hop is at least 1";
+    else if (target < 1) *msg = "target is at least 1";
+    else if (overlap < 0) *msg = "overlap is at least 0";
+    else if ((long long)target + 2LL * overlap > INT_MAX) *msg = "target + 2 * overlap exceeds the step counter";
+    if (!msg->empty()) return WRNN_EINVAL;
+    p.folds.assign(U, 0);
+    p.first_row.assign(U, 0);
+    p.ls.clear();
+    p.round_of.clear();
+    p.Lf = target + 2 * overlap;
+    const long long stride = (long long)target + overlap;
+    long long F = 0;
+    for (int i = 0; i < U; ++i) {
+        const std::string who = "utterance " + std::to_string(i);
+        const long long L = (long long)frames[i] * hop;
+        if (frames[i] < 21)
+            *msg = who + " has " + std::to_string(frames[i]) + " frames: fewer than 21 (the fade-out, as wrnn_postprocess)";
+        else if (L > (1LL << 30)) *msg = who + ": hop * frames exceeds the step counter";
+        else if (L < overlap) *msg = who + ": hop * frames (" + std::to_string(L) + ") is less than the overlap";
+        if (!msg->empty()) return WRNN_EINVAL;
+        // fold_with_overlap's count (condition.hip: fold_geometry, what wrnn_cond_shape returns)
+        long long n = (L - overlap) / stride;
+        if (L - (n * stride + overlap) != 0) ++n;
+        if (n < 1) *msg = who + ": hop * frames equals the overlap: no fold";
+        else if ((n - 1) * stride + p.Lf > INT_MAX) *msg = who + ": its folds exceed the step counter";
+        else if (F + n > INT_MAX) *msg = "the list has more folds than the row counter holds";
+        if (!msg->empty()) return WRNN_EINVAL;
+        p.folds[i] = (int)n;
+        p.first_row[i] = (int)F;
+        F += n;
+    }
+    p.F = (int)F;
+    p.slots = slots == 0 ? (int)std::min<long long>(kMRowsMax, F) : slots;
+    const long long rounds = (F + p.slots - 1) / p.slots;
+    if (rounds * p.Lf > INT_MAX) {
+        *msg = "the common timeline (rounds * (target + 2 * overlap)) exceeds the step counter";
+        return WRNN_EINVAL;
+    }
+    for (long long q = 0; q < rounds; ++q) {
+        const int rows = (int)std::min<long long>(p.slots, F - q * p.slots);
+        const int Lc_max = wrnn_wide_steps_per_launch(rows, p.Lf, raw ? 1 : 0);
+        if (Lc_max < 1) {
+            *msg = "wrnn_wide_steps_per_launch refused the launch";
+            return WRNN_EINVAL;
+        }
+        for (int off = 0; off < p.Lf; off += Lc_max) {
+            p.ls.push_back({off, std::min(Lc_max, p.Lf - off), rows});
+            p.round_of.push_back((int)q);
+        }
+    }
+    return WRNN_OK;
+}
+
+int wrnn_list_folds_plan(const int *frames, int U, int hop, int target, int overlap, int slots, int raw, int *folds,
+                         int *first_row, int *launch_first, int *launch_steps, int *launch_rows, int cap) {
+    if (!frames) return cond_fail(WRNN_EINVAL, "need frames");
+    std::string msg;
+    FoldListPlan p;
+    if (int rc = fold_list_plan(frames, U, hop, target, overlap, slots, raw != 0, p, &msg)) return cond_fail(rc, msg);
+    for (int i = 0; i < U; ++i) {
+        if (folds) folds[i] = p.folds[i];
+        if (first_row) first_row[i] = p.first_row[i];
+    }
+    for (size_t j = 0; j < p.ls.size() && (int)j < cap; ++j) {
+        if (launch_first) launch_first[j] = p.round_of[j] * p.Lf + p.ls[j].off;
+        if (launch_steps) launch_steps[j] = p.ls[j].Lc;
+        if (launch_rows) launch_rows[j] = p.ls[j].rows;
+    }
+    return (int)p.ls.size();
+}
+
+int wrnn_generate_list_folds(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *const *mel, const float *const *aux,
+                             const int *T, int U, int target, int overlap, int slots, const float *const *noise,
+                             uint64_t seed, int64_t row_offset, float *const *out, void *stream) {
+    if (!h) return WRNN_EINVAL;
+    if (!h->ready) return fail(h, WRNN_ENOWEIGHTS, "weights not (fully) set");
+    // ---- every argument of every utterance, before anything is queued or any workspace touched
+    if (!ucfg || !mel || !T || !out || U < 1) return fail(h, WRNN_EINVAL, "need ucfg, mel, T, out and U >= 1");
+    int hop = 1, nJ = 1, jlo = 0;
+    std::vector<float> coef;
+    if (int rc = wide_list_handle_args(h, ucfg, aux, &hop, &nJ, &jlo, coef)) return rc;
+    const bool raw = h->cfg.mode == WRNN_MODE_RAW;
+    const int K = raw ? kMRawNC : 11;
+    const int A4 = h->CD - h->cfg.feat_dims;
+    std::string msg;
+    FoldListPlan p;
+    if (int rc = fold_list_plan(T, U, hop, target, overlap, slots, raw, p, &msg)) return fail(h, rc, msg);
+    int Tmax = 0;
+    for (int i = 0; i < U; ++i) {
+        if (!mel[i] || !out[i] || (A4 > 0 && !aux[i]) || (noise && !noise[i]))
+            return fail(h, WRNN_EINVAL, "utterance " + std::to_string(i) + ": need mel, aux, out (and its noise)");
+        Tmax = std::max(Tmax, T[i]);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+
+    // ---- every workspace grown before anything is queued (growing one waits for the device)
+    const int N = kXcdWgs * kMRing;
+    std::vector<size_t> ft_off(U), at_off(U);
+    size_t arena = 0, ntab = 0, t_need = 0, nz_need = 0;
+    for (int i = 0; i < U; ++i) {
+        ft_off[i] = arena;
+        arena += (size_t)(T[i] + nJ - 1) * N;
+        at_off[i] = arena;
+        arena += (size_t)(T[i] + 1) * N;
+    }
+    for (const WideLaunch &l : p.ls) {
+        ntab += (size_t)l.rows;
+        t_need = std::max(t_need, (size_t)(l.Lc + 1) * l.rows * N);   // one row on: the kernel's look-ahead load
+        nz_need = std::max(nz_need, (size_t)(l.Lc + 1) * l.rows * K);
+    }
+    const int fmax = std::max(Tmax + nJ - 1, Tmax + 1);
+    if (grow(h, h->d_frec, h->frec_cap, (size_t)fmax * h->CD) || grow(h, h->d_X, h->X_cap, (size_t)fmax * h->KXc) ||
+        grow(h, h->d_larena, h->larena_cap, arena) || grow(h, h->d_T, h->T_cap, t_need) ||
+        grow(h, h->d_xmnoise, h->xmnoise_cap, nz_need) ||
+        grow(h, h->d_lstate, h->lstate_cap, (size_t)p.F * kXcdWgs * kMRowStateW))   // one record per fold
+        return WRNN_EHIP;
+    if (int rc = wide_list_prepare(h, coef, st)) return rc;
+    if (int rc = wide_tab_reserve(h, ntab + fold_tab_records(ntab))) return rc;
+
+    // ---- the row tables of all launches, the fold records behind them in the same order
+    FoldRow *h_folds = reinterpret_cast<FoldRow *>(h->h_wtab + ntab);
+    const int stride = target + overlap;
+    size_t at = 0;
+    for (size_t j = 0; j < p.ls.size(); ++j) {
+        const WideLaunch &l = p.ls[j];
+        int i = 0;   // the utterance of the round's first fold, then onwards: folds are utterance-major
+        const int g0 = p.round_of[j] * p.slots;
+        while (i + 1 < U && p.first_row[i + 1] <= g0) ++i;
+        for (int r = 0; r < l.rows; ++r) {
+            const int g = g0 + r;
+            while (g >= p.first_row[i] + p.folds[i]) ++i;
+            const int f = g - p.first_row[i], nf = p.folds[i];
+            if (at >= ntab || i >= U || f < 0) return fail(h, WRNN_EINVAL, "folded list: the row tables do not match the plan");
+            XcdmRow row{};
+            row.ft = h->d_larena + ft_off[i];
+            row.at = h->d_larena + at_off[i];
+            row.fr_ld = N;
+            row.noise = noise ? noise[i] + ((size_t)l.off * nf + f) * K : nullptr;   // [Lf][folds_i][K]
+            row.noise_ld = (long long)nf * K;
+            row.seed = seed;
+            row.prow = row_offset + g;
+            row.out = out[i] + (size_t)f * p.Lf + l.off;                             // [folds_i][Lf]
+            row.state = h->d_lstate + (size_t)g * kXcdWgs * kMRowStateW;             // the fold's own record
+            row.ft_base = row.at_base = 0;
+            row.t0 = l.off;                                                          // the fold-local step (Philox)
+            row.resume = l.off > 0;
+            h_folds[at] = FoldRow{f * stride + l.off, T[i]};
+            h->h_wtab[at++] = row;
+        }
+    }
+    if (at != ntab) return fail(h, WRNN_EINVAL, "folded list: the row tables do not match the plan");
+
+    // ---- queuing begins
+    if (int rc = wide_list_frame_terms(h, mel, aux, T, U, hop, nJ, jlo, ft_off, at_off, st)) return rc;
+    return wide_run_launches(h, p.ls, ntab, h->d_coef, hop, nJ, raw, K, st, true);
 }
 
 // The group of one, through the launch-wide windowed kernel (wide sessions: the wide group of one)

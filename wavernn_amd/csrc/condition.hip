@@ -279,6 +279,55 @@ __global__ void postprocess_list_kernel(const wrnn_post_entry *__restrict__ tab,
     wave[e.dst + t] = v;
 }
 
+// postprocess_kernel's batched case for every utterance of a list in one launch
+// (wrnn_postprocess_list_folds): workgroup (x, y) takes samples [256·x, 256·x + 256) of table entry y —
+// its folds' fp32 loop output [rows][steps], its wave_len and the offset of its float64 waveform.
+// The fold length, the overlap and what follows from them are call-wide.  Per sample the operations,
+// their order and the linspace elements are postprocess_kernel's (contraction off in both).
+struct PostFoldsArgs {
+    const wrnn_post_fold_entry *tab;
+    double *wave;
+    int steps, ov, stride, silence, xfade_len, fade_len, mu_law;
+    double mu;            // n_classes − 1
+    double fin_step, fout_step;
+};
+
+__global__ void postprocess_list_folds_kernel(PostFoldsArgs a) {
+#pragma clang fp contract(off)
+    const wrnn_post_fold_entry e = a.tab[blockIdx.y];
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= e.wave_len) return;
+    auto mulaw = [&](double y) {
+        // np.sign(y) / mu * ((1 + mu) ** np.abs(y) - 1)   (utils/dsp.py:102)
+        const double sg = y > 0.0 ? 1.0 : (y < 0.0 ? -1.0 : 0.0);
+        return sg / a.mu * (pow(a.mu + 1.0, fabs(y)) - 1.0);
+    };
+    // unfolded[start:end] += y[i] for i = 0, 1, ... (:399-403) after both fades (:396-397)
+    double v = 0.0;
+    const int fh = min(t / a.stride, e.rows - 1);
+    for (int f = max(fh - 1, 0); f <= fh; ++f) {
+        const int k = t - f * a.stride;
+        if (k < 0 || k >= a.steps) continue;
+        double y = (double)e.y[(size_t)f * a.steps + k];
+        if (a.mu_law) y = mulaw(y);
+        if (k < a.ov) {
+            const int q = k - a.silence;
+            const double tt = q < 0 ? 0.0 : linspace_at(q, a.xfade_len, -1.0, 1.0, a.fin_step);
+            y = y * (q < 0 ? 0.0 : sqrt(0.5 * (1.0 + tt)));
+        }
+        if (k >= a.steps - a.ov) {
+            const int q = k - (a.steps - a.ov) - a.silence;
+            const double tt = q < 0 ? 0.0 : linspace_at(q, a.xfade_len, -1.0, 1.0, a.fin_step);
+            y = y * (q < 0 ? 1.0 : sqrt(0.5 * (1.0 - tt)));
+        }
+        v = v + y;
+    }
+    // output[-20·hop:] *= np.linspace(1, 0, 20·hop)   (:255-258)
+    const int q = t - (e.wave_len - a.fade_len);
+    if (q >= 0) v = v * linspace_at(q, a.fade_len, 1.0, 0.0, a.fout_step);
+    a.wave[e.dst + t] = v;
+}
+
 // ---- content fingerprints (wrnn_fingerprint): one 64-bit sum per tensor, block (chunk, tensor)
 constexpr int kFpMax = 64;        // tensors per launch (the pointer table travels as kernel arguments)
 constexpr int kFpChunks = 32;     // workgroups per tensor
@@ -488,6 +537,36 @@ int wrnn_postprocess_list(const wrnn_post_entry *entries, int U, int max_wave_le
     hipLaunchKernelGGL(postprocess_list_kernel, dim3((max_wave_len + 255) / 256, U), dim3(256), 0, (hipStream_t)stream,
                        entries, wave, fade_len, (0.0 - 1.0) / (double)(fade_len > 1 ? fade_len - 1 : 1), mu_law != 0 ? 1 : 0,
                        (double)(n_classes - 1));
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WRNN_OK : cond_fail(WRNN_EHIP, hipGetErrorString(e));
+}
+
+int wrnn_postprocess_list_folds(const wrnn_post_fold_entry *entries, int U, int steps, int overlap, int max_wave_len,
+                                int mu_law, int n_classes, int fade_len, double *wave, void *stream) {
+    using namespace wrnn;
+    if (!entries || !wave || U < 1 || U > 65535) return cond_fail(WRNN_EINVAL, "need entries, wave and 1..65535 utterances");
+    if (steps < 1) return cond_fail(WRNN_EINVAL, "bad arguments");
+    if (fade_len < 1 || fade_len > max_wave_len)
+        return cond_fail(WRNN_EINVAL, "operands could not be broadcast together: the fade-out (20*hop_length = " +
+                                          std::to_string(fade_len) + ") is longer than the waveform (" +
+                                          std::to_string(max_wave_len) + ")");
+    const int target = steps - 2 * overlap;
+    if (overlap < 0 || target < 1) return cond_fail(WRNN_EINVAL, "bad overlap for the fold length");
+    PostFoldsArgs a{};
+    a.tab = entries;
+    a.wave = wave;
+    a.steps = steps;
+    a.ov = overlap;
+    a.stride = target + overlap;
+    a.silence = overlap / 2;
+    a.xfade_len = overlap - a.silence;
+    a.fade_len = fade_len;
+    a.mu_law = mu_law != 0 ? 1 : 0;
+    a.mu = (double)(n_classes - 1);
+    a.fin_step = 2.0 / (double)(a.xfade_len > 1 ? a.xfade_len - 1 : 1);
+    a.fout_step = (0.0 - 1.0) / (double)(fade_len > 1 ? fade_len - 1 : 1);
+    hipLaunchKernelGGL(postprocess_list_folds_kernel, dim3((max_wave_len + 255) / 256, U), dim3(256), 0,
+                       (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? WRNN_OK : cond_fail(WRNN_EHIP, hipGetErrorString(e));
 }

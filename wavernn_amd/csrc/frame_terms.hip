@@ -18,6 +18,7 @@
 
 #include "fatchord_xcd.h"
 #include "fatchord_xcdm.h"
+#include "frame_terms.h"
 
 namespace wrnn {
 
@@ -239,6 +240,69 @@ hipError_t launch_terms_interp_wide(const XcdmRow *rows, const float *coef, floa
                                     int nt, hipStream_t st) {
     const dim3 grid(nb * ((nt + kInterpSteps - 1) / kInterpSteps), (N / 4 + kInterpThreads - 1) / kInterpThreads);
     hipLaunchKernelGGL(terms_interp_wide_kernel, grid, dim3(kInterpThreads), 0, st, rows, coef, T, N, hop, nJ, nb, nt);
+    return hipGetLastError();
+}
+
+// ---- folded lists (capi.cpp: wrnn_generate_list_folds): the table-driven pass for fold rows --------
+// Launch row k is one fold of some utterance: its XcdmRow gives the utterance's whole frame-term
+// stores (base 0, fr_ld floats between frame rows), its FoldRow the utterance position of launch
+// step 0 and the utterance's frame count.  A fold may start inside a frame (target + overlap need
+// not be a multiple of hop) and its last steps may lie past the utterance: from position hop·NF on
+// the terms are the row AT[NF] = W·[0 | 0 | 1] alone and no FT row is read, exactly as
+// terms_interp_kernel does it.  Per sample the fmaf order is terms_interp_kernel's, so a fold row's
+// terms are the bits wrnn_generate_frames forms for the same fold.
+__global__ __launch_bounds__(kInterpThreads) void terms_interp_folds_kernel(const XcdmRow *rows, const FoldRow *folds,
+                                                                             const float *coef, float *T, int N, int hop,
+                                                                             int nJ, int nb, int nt) {
+    const int c4 = blockIdx.y * kInterpThreads + threadIdx.x;   // float4 column
+    if (4 * c4 >= N) return;
+    const int nblk = (nt + kInterpSteps - 1) / kInterpSteps;
+    const int k = blockIdx.x / nblk, tb = (blockIdx.x - k * nblk) * kInterpSteps;
+    const XcdmRow &r = rows[k];
+    const int NF = folds[k].NF;
+    const int s0 = folds[k].pos0, L_utt = NF * hop;           // the plan keeps every position below 2^31
+    const size_t rs = (size_t)r.fr_ld;                          // frame-row stride
+    const float *A0 = r.at + 4 * c4, *F0 = r.ft + 4 * c4;
+    float4 fr[kInterpMaxJ], ar = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int loaded = -1;
+    for (int i = 0; i < kInterpSteps; ++i) {
+        const int tl = tb + i;
+        if (tl >= nt) break;
+        const int p = s0 + tl;
+        const int f = p < L_utt ? p / hop : NF;                 // NF: past the utterance (W·[0 | 0 | 1])
+        if (f != loaded) {
+            ar = *reinterpret_cast<const float4 *>(A0 + (size_t)f * rs);
+            if (f < NF) {
+#pragma unroll
+                for (int j = 0; j < kInterpMaxJ; ++j)
+                    if (j < nJ) fr[j] = *reinterpret_cast<const float4 *>(F0 + (size_t)(f + j) * rs);
+            }
+            loaded = f;
+        }
+        float4 acc = ar;
+        if (f < NF) {
+            const float *cf = coef + (size_t)(p - f * hop) * nJ;
+#pragma unroll
+            for (int j = 0; j < kInterpMaxJ; ++j) {
+                if (j < nJ) {
+                    const float w = cf[j];
+                    acc.x = fmaf(w, fr[j].x, acc.x);
+                    acc.y = fmaf(w, fr[j].y, acc.y);
+                    acc.z = fmaf(w, fr[j].z, acc.z);
+                    acc.w = fmaf(w, fr[j].w, acc.w);
+                }
+            }
+        }
+        *reinterpret_cast<float4 *>(T + ((size_t)tl * nb + k) * N + 4 * c4) = acc;
+    }
+}
+
+// Every row's stores hold FT rows [0, NF + nJ − 1) and AT rows [0, NF]; N % 4 == 0, nJ <= kInterpMaxJ
+hipError_t launch_terms_interp_folds(const XcdmRow *rows, const FoldRow *folds, const float *coef, float *T, int N,
+                                     int hop, int nJ, int nb, int nt, hipStream_t st) {
+    const dim3 grid(nb * ((nt + kInterpSteps - 1) / kInterpSteps), (N / 4 + kInterpThreads - 1) / kInterpThreads);
+    hipLaunchKernelGGL(terms_interp_folds_kernel, grid, dim3(kInterpThreads), 0, st, rows, folds, coef, T, N, hop, nJ, nb,
+                       nt);
     return hipGetLastError();
 }
 

@@ -333,7 +333,12 @@ class WaveRNN(nn.Module):
         same list of float64 waveforms.  Utterance i's rows are keyed row_offset + (rows of the
         utterances before it) + j, so under Philox `generate_many(mels, seed=s)[i]` equals
         `generate(mels[i], seed=s, row_offset=<that first row>)` bit for bit.  `noise`, when given,
-        is [L_max][rows][K] in that row order."""
+        is [L_max][rows][K] in that row order.
+
+        Unequal lengths with batched=True: prefer generate_list(mels, wide=True, batched=True, target=,
+        overlap=) — the same rows and Philox keys, but the conditioning terms stay at frame rate and the
+        folds fill the 128 many-row slots, where this entry materialises sample-rate conditioning for
+        every fold (conditioning_many)."""
         self.eval()
         mu_law = mu_law if self.mode == 'RAW' else False
         start = time.time()
@@ -370,7 +375,8 @@ class WaveRNN(nn.Module):
     def generate_list(self, mels: Sequence, save_paths: Optional[Sequence] = None, *, noise=None,
                       seed: Optional[int] = None, row_offset: int = 0, lanes: Optional[int] = None,
                       verbose: bool = False, wide: bool = False, slots: Optional[int] = None,
-                      mu_law: bool = True) -> List[np.ndarray]:
+                      mu_law: bool = True, batched: bool = False, target: int = 11000,
+                      overlap: int = 550) -> List[np.ndarray]:
         """generate(mels[i], None, False, …) for a list of utterances of ANY lengths (each (1, feat,
         T_i), T_i ≥ 21; unbatched: no folds) in one call: the eight XCDs are eight lanes, each runs
         a queue of utterances back to back inside the persistent launch (longest first, each to the
@@ -398,7 +404,30 @@ class WaveRNN(nn.Module):
         MoL lies within 2e-5 of the oracle on the same draws and, with `seed`, within MoL tolerance
         of generate(mels[i], seed=s, row_offset=r + i), but is NOT bit-identical to the narrow list
         or to generate() (another kernel); RAW class labels are the oracle's and generate()'s on the
-        same draws bit for bit, so with mu_law=False every sample before the fade is exact."""
+        same draws bit for bit, so with mu_law=False every sample before the fade is exact.
+
+        Folded lists.  `batched=True` (with `wide=True`; the narrow lanes have no folded form) is the
+        reference's default way to vocode, for a list: every utterance is cut into folds of
+        `target + 2·overlap` steps and the folds of ALL utterances fill the slots (C-ABI
+        wrnn_generate_list_folds: fold g of the utterance-major numbering runs in round g // slots as
+        launch row g % slots), then one cross-fade launch (wrnn_postprocess_list_folds) and one copy
+        to the host → what generate(mels[i], None, True, target, overlap, mu_law) returns, (T_i − 1)·hop
+        float64 samples each.  `noise[i]` is [target + 2·overlap][folds_i][K], generate()'s layout for
+        that utterance alone; under Philox fold j of utterance i is row row_offset + (folds of the
+        utterances before it) + j, generate_many's key.  A long utterance spreads over many slots
+        instead of holding one, so this is the form for lists with long or very unequal members; for
+        hundreds of SHORT utterances (a fold or two each) the unbatched wide list does the same work
+        without the overlaps' extra steps.  Promises: independence of company as above (bit-identical
+        to the folded list of mels[i] alone with row_offset + its first row); RAW fold outputs equal
+        generate()'s bit for bit on the same draws; MoL within √2·2e-5 of the oracle on the same draws
+        (two cross-faded fold samples) and, with `seed`, within √2·1e-5 of generate(..., True, target,
+        overlap, ..., seed=s, row_offset=r + first row)."""
+        if batched:
+            if not wide:
+                raise ValueError("batched=True needs wide=True: folds run on the many-row slots, the narrow lanes have "
+                                 "no folded form")
+            return self._generate_list_folds(mels, save_paths, noise, seed, row_offset, lanes, slots, mu_law, target,
+                                             overlap, verbose)
         if wide:
             return self._generate_list_wide(mels, save_paths, noise, seed, row_offset, lanes, slots, mu_law, verbose)
         self.eval()
@@ -467,6 +496,54 @@ class WaveRNN(nn.Module):
         if verbose:
             longest = max(o.shape[0] for o in outs)
             self.gen_display(longest - 1, longest, len(outs), start)
+        for i, output in enumerate(outputs):
+            if save_paths is not None and save_paths[i] is not None:
+                dsp.save_wav(output, save_paths[i], self.sample_rate)
+        self.train()
+        return outputs
+
+    def _generate_list_folds(self, mels, save_paths, noise, seed, row_offset, lanes, slots, mu_law, target, overlap,
+                             verbose):
+        """generate_list(wide=True, batched=True): every refusal that needs no device work comes before any launch."""
+        if lanes is not None:
+            raise ValueError("lanes belongs to the narrow list: a folded list takes slots (1..128)")
+        if slots is not None and not 1 <= int(slots) <= 128:
+            raise ValueError("slots is 1..128 (16 per XCD)")
+        target, overlap = int(target), int(overlap)
+        if target < 1 or overlap < 0:
+            raise ValueError(f"target is at least 1 and overlap at least 0, not ({target}, {overlap})")
+        self.eval()
+        mu_law = mu_law if self.mode == 'RAW' else False
+        start = time.time()
+        with torch.no_grad():
+            ms = self._mel_list(mels)
+            if noise is not None and len(noise) != len(ms):
+                raise ValueError(f"noise holds one [target + 2·overlap][folds][{self.noise_width()}] array per utterance")
+            if any(m.shape[2] < 21 for m in ms):   # before the MelResNet launches: nothing is queued
+                raise ValueError("every utterance needs at least 21 frames (the fade-out)")
+            if any(m.shape[2] * self.hop_length < overlap for m in ms):
+                raise ValueError("every utterance needs at least `overlap` samples")
+            Lf = target + 2 * overlap
+            folds = [self.rows_of(m.shape[2], True, target, overlap) for m in ms]
+            loop = self.loop_handle()
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            dev = ms[0].device
+            nz = None if noise is None else [torch.as_tensor(z, dtype=torch.float32).to(dev).contiguous() for z in noise]
+            if nz is not None:
+                for i, z in enumerate(nz):
+                    if tuple(z.shape) != (Lf, folds[i], self.noise_width()):
+                        raise ValueError(f"noise[{i}] must be [{Lf}][{folds[i]}][{self.noise_width()}]")
+            fr = [self.frames(m) for m in ms]   # one MelResNet launch per utterance, at its own shape
+            outs = loop.generate_list_folds(self._upsample_spec(), [f[0] for f in fr], [f[1] for f in fr], target,
+                                            overlap, slots=slots, noise=nz, seed=seed, row_offset=row_offset)
+            wave, off = condition.postprocess_list_folds(outs, overlap, [f[2] for f in fr], mu_law, self.n_classes,
+                                                         20 * self.hop_length)
+            host = wave.cpu().numpy()
+            outputs = [host[o:o + f[2]].copy() for o, f in zip(off, fr)]
+        self.last_gen_seconds = time.time() - start
+        if verbose:
+            self.gen_display(Lf - 1, Lf, sum(folds), start)
         for i, output in enumerate(outputs):
             if save_paths is not None and save_paths[i] is not None:
                 dsp.save_wav(output, save_paths[i], self.sample_rate)

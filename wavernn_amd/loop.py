@@ -413,6 +413,66 @@ class FatchordLoop:
             self.check(stream)
         return outs
 
+    def generate_list_folds(self, spec, mels, auxs, target: int = 11000, overlap: int = 550,
+                            slots: Optional[int] = None, noise=None, seed: int = 0, row_offset: int = 0, stream=None,
+                            check: bool = True) -> list:
+        """A list of unequal utterances fold-batched on the many-row kernel (C-ABI
+        wrnn_generate_list_folds): every utterance is cut into folds of target + 2·overlap steps and
+        the folds of all utterances, numbered utterance-major, run as the rows of the grouped launches
+        — fold g in round g // slots as launch row g % slots (`slots` 1..128, default min(128, folds)).
+        mels / auxs as generate_list_wide → per utterance the fold outputs [folds_i][target + 2·overlap]
+        fp32 on the GPU, the rows generate_frames(spec, mels[i], auxs[i], target, overlap,
+        row_offset=row_offset + first_row[i]) runs (RAW: bit for bit on the same draws; MoL: another
+        instantiation of the kernel, within the wide bound).  `noise`: per-utterance
+        [target + 2·overlap][folds_i][K] draws, generate_frames' layout for that utterance alone.
+        Utterance i's output does not depend on the other utterances, their order, `slots` or
+        WRNN_TERMS_MB.  Refusals before anything is queued raise ValueError (bad arguments) or
+        NotImplementedError (a loop without the grouped many-row form) and leave the handle as it was."""
+        if getattr(self, "_padded", False):
+            raise NotImplementedError("lists need rnn / fc / aux dims that are multiples of 4")
+        U = len(mels)
+        if U < 1 or len(auxs) != U or (noise is not None and len(noise) != U):
+            raise ValueError("mels, auxs (and noise) must be non-empty sequences of one length")
+        if slots is not None and not 1 <= int(slots) <= WIDE_ROWS:
+            raise ValueError(f"slots is 1..{WIDE_ROWS} (16 per XCD), not {slots!r}")
+        for name, ts, C in (("mel", mels, self.feat_dims), ("aux", auxs, 4 * self.aux_dims)):
+            for t in ts:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                        and t.dim() == 3 and t.shape[0] == 1 and t.shape[1] == C):
+                    raise ValueError(f"every {name} must be a contiguous fp32 CUDA tensor [1][{C}][T]")
+        T = [int(m.shape[2]) for m in mels]
+        if any(a.shape[2] != t for a, t in zip(auxs, T)):
+            raise ValueError("an aux has another frame count than its mel")
+        target, overlap = int(target), int(overlap)
+        try:
+            folds, _, _ = list_folds_plan(T, spec.hop, target, overlap, slots, raw=self.mode == "RAW")
+        except nat.WrnnError as e:
+            raise ValueError(str(e)) from None
+        Lf = target + 2 * overlap
+        if noise is not None:
+            for i, z in enumerate(noise):
+                if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous()) or \
+                        tuple(z.shape) != (Lf, folds[i], self.noise_k):
+                    raise ValueError(f"noise[{i}] must be a contiguous fp32 CUDA tensor [{Lf}][{folds[i]}][{self.noise_k}]")
+        dev = mels[0].device
+        outs = [torch.empty(n, Lf, dtype=torch.float32, device=dev) for n in folds]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        vps = ctypes.c_void_p * U
+        rc = nat.lib().wrnn_generate_list_folds(
+            self._h, ctypes.byref(spec.cfg), vps(*[m.data_ptr() for m in mels]), vps(*[a.data_ptr() for a in auxs]),
+            (ctypes.c_int * U)(*T), U, target, overlap, 0 if slots is None else int(slots),
+            vps(*[z.data_ptr() for z in noise]) if noise is not None else None,
+            ctypes.c_uint64(seed & (2 ** 64 - 1)), row_offset, vps(*[o.data_ptr() for o in outs]), stream)
+        if rc == -6:   # WRNN_EUNSUPPORTED
+            raise NotImplementedError((nat.lib().wrnn_last_error(self._h) or b"").decode(errors="replace"))
+        if rc == -1:   # WRNN_EINVAL: nothing was queued
+            raise ValueError((nat.lib().wrnn_last_error(self._h) or b"").decode(errors="replace"))
+        nat.check(self._h, rc)
+        if check:
+            self.check(stream)
+        return outs
+
     def push_streams(self, pushes, stream=None, check: bool = True) -> list:
         """Advance several sessions of this loop in one call (C-ABI wrnn_stream_push_group): `pushes`
         is a sequence of (FatchordStream, mel or None, final), each member with its own frames and
@@ -599,6 +659,34 @@ def list_wide_plan(frames, slots: Optional[int] = None, hop: int = 275, raw: boo
     first, ls, lr = (ctypes.c_int * count)(), (ctypes.c_int * count)(), (ctypes.c_int * count)()
     nat.check_cond(min(0, nat.lib().wrnn_list_wide_plan(*args, first, ls, lr, count)))
     return list(slot_of)[:U], list(pos)[:U], list(sf)[:slots], list(zip(first, ls, lr))
+
+
+def list_folds_plan(frames, hop: int = 275, target: int = 11000, overlap: int = 550, slots: Optional[int] = None,
+                    raw: bool = False) -> Tuple[list, list, list]:
+    """The schedule of a folded list call (C-ABI wrnn_list_folds_plan, host only): (folds, first_row,
+    launches) for utterances of `frames` frames at `hop` steps per frame, cut into folds of
+    target + 2·overlap steps.  folds[i] is utterance i's fold count (what UpsampleSpec.shape gives),
+    first_row[i] the number of its first fold in the utterance-major numbering; fold g runs in round
+    g // slots as launch row g % slots (`slots` 1..128, default min(128, all folds)).  `launches`
+    holds one (first step on the common timeline, steps, rows) per persistent launch: round q covers
+    steps [q·Lf, (q + 1)·Lf) with Lf = target + 2·overlap, cut at wide_steps_per_launch(rows of the
+    round, Lf, raw) steps.  Raises WrnnError(WRNN_EINVAL) for an empty list, slots outside 1..128,
+    hop < 1, target < 1, overlap < 0, an utterance under 21 frames or shorter than the overlap, or
+    counts past 32 bits."""
+    if slots is not None and int(slots) == 0:     # the C entry's 0 is this function's None
+        raise nat.WrnnError(-1, f"slots is 1..{WIDE_ROWS} (16 per XCD)")
+    frames = [int(f) for f in frames]
+    U = len(frames)
+    n = max(U, 1)
+    folds, first = (ctypes.c_int * n)(), (ctypes.c_int * n)()
+    args = ((ctypes.c_int * n)(*frames), U, int(hop), int(target), int(overlap), 0 if slots is None else int(slots),
+            int(bool(raw)), folds, first)
+    count = nat.lib().wrnn_list_folds_plan(*args, None, None, None, 0)
+    if count < 0:
+        nat.check_cond(count)
+    lf, ls, lr = (ctypes.c_int * count)(), (ctypes.c_int * count)(), (ctypes.c_int * count)()
+    nat.check_cond(min(0, nat.lib().wrnn_list_folds_plan(*args, lf, ls, lr, count)))
+    return list(folds)[:U], list(first)[:U], list(zip(lf, ls, lr))
 
 
 def stream_lookahead(spec) -> int:
