@@ -1,4 +1,4 @@
-"""The frame-rate form of the UpsampleNetwork's mel path (wrnn_frame_weights, csrc/capi.cpp;
+"""The frame-rate form of the UpsampleNetwork's mel path (wrnn_frame_weights, csrc/capi_loops.cpp;
 csrc/frame_terms.hip): mel_up(f·hop + φ) = Σ_k coef[φ][k]·mel[f + k + jlo] must reproduce the
 stage-wise Stretch2d/Conv2d cascade (fatchord_version.py:64-89, restated by oracle.upsample) —
 host-only, no GPU.  The GPU side (the terms formed from these weights inside the loop entry) is

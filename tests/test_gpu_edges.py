@@ -18,7 +18,7 @@ from wavernn_amd.pruning import prune_state
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-# WRNN_PATH → wrnn_info.last_path (capi.cpp, wrnn_generate)
+# WRNN_PATH → wrnn_info.last_path (capi_loops.cpp, wrnn_generate)
 MOL_PATHS = {"latency": 1, "rows": 2, "split": 4, "xcd": 5, "xcdm": 7}
 RAW_PATHS = {"latency": 1, "rows": 2, "xcdm": 7}
 TINY_BUDGET_MB = "0.0001"   # every time chunk one step

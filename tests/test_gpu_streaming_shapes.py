@@ -106,7 +106,7 @@ def test_every_geometry_dense(geom, total):
 # ---- 2. store swaps under held-back audio ---------------------------------------------------------
 def _store_swaps(hop, pad, jlo, nJ, frames, U):
     """The session's bookkeeping for `frames` 1-frame pushes and finish(), total unknown, restated
-    from capi.cpp (win_reserve; stream_push's d_y branch): ([FT swaps], [AT swaps] as (frames
+    from capi_stream.cpp (win_reserve; stream_push's d_y branch): ([FT swaps], [AT swaps] as (frames
     received, rows copied), [d_y swaps] as (frames received, samples held, samples emitted))."""
     look, jhi = pad + 1, jlo + nJ - 1
 

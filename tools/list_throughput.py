@@ -17,7 +17,7 @@ median, min and max of --reps calls after one untimed warm-up of the same shapes
 alternating inside every repeat), samples/s and × real time from the median, the device ms between
 the loop's timing events (frame terms + per-round interpolation + persistent launches; wall − loop
 is MelResNet, host work and the float64 post), the persistent launches per call (restated from the
-launch loops of csrc/capi.cpp for the WRNN_TERMS_MB in effect), and for (c) the lane occupancy
+launch loops of csrc/capi_loops.cpp, capi_lists.cpp and capi_stream.cpp for the WRNN_TERMS_MB in effect), and for (c) the lane occupancy
 Σ L_i / (lanes · longest lane timeline) and the MelResNet (frames()) time of the list measured on
 its own.  (a) and (c) must produce identical audio; (d) runs another kernel: its largest difference
 from the first other way that ran is reported.  For (d): the slots, the slot occupancy Σ steps /
@@ -66,13 +66,13 @@ def _budget():
 
 
 def launches_single(L, rows, kxc, N=N_XCD):
-    """generate_xcd_rows (capi.cpp): rows <= 8, time chunks of floor(budget / (rows·(N + KXc)) − 1) steps."""
+    """generate_xcd_rows (capi_loops.cpp): rows <= 8, time chunks of floor(budget / (rows·(N + KXc)) − 1) steps."""
     lc = int(max(1.0, min(float(L), _budget() / (rows * (N + kxc)) - 1.0)))
     return -(-L // lc)
 
 
 def launches_many(L, rows, kxc, N=N_XCD):
-    """generate_many's route: up to 8 rows the one-row kernel, from 9 the many-row kernel (capi.cpp:
+    """generate_many's route: up to 8 rows the one-row kernel, from 9 the many-row kernel (capi_loops.cpp:
     generate_xcdm, Philox draws: 11 more floats per row-step)."""
     if rows <= 8 or N != N_XCD:     # the sparse model has no many-row kernel: eight rows at a time
         return sum(launches_single(L, min(8, rows - b0), kxc, N) for b0 in range(0, rows, 8))

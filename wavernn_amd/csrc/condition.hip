@@ -18,6 +18,7 @@
 #include <string>
 
 #include "wavernn_amd.h"
+#include "condition.h"
 
 namespace wrnn {
 

@@ -1,5 +1,6 @@
-// Shared between capi.cpp and deepmind_rows.hip: the dual-softmax (deepmind_version.py) loop.
+// Shared between the host side (capi*.cpp) and deepmind_rows.hip: the dual-softmax (deepmind_version.py) loop.
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #include "fatchord_rows.h"
@@ -92,5 +93,10 @@ __host__ __device__ inline DmLds dm_lds_layout(int slab_total, int B, int TB, in
     l.total = o;
     return l;
 }
+
+// host launchers (deepmind_rows.hip)
+hipError_t launch_dm(const DmArgs &a, const DmGroup *g1, size_t lds_bytes, hipStream_t st);
+hipError_t prepare_dm_kernel(int max_lds_bytes);
+hipError_t dm_occupancy(int *blocks_per_cu, size_t lds_bytes);
 
 }  // namespace wrnn

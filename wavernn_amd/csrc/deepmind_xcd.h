@@ -1,4 +1,4 @@
-// Shared between the host launcher (capi.cpp) and deepmind_xcd.hip: the XCD-resident kernel of the
+// Shared between the host side (capi*.cpp) and deepmind_xcd.hip: the XCD-resident kernel of the
 // dual coarse/fine softmax WaveRNN (models/deepmind_version.py:75-165) — up to 4 rows
 // (utterances) on each XCD, 32 per launch, all stepping through one copy of the weights held in
 // the XCD's 32 CUs as fp32 MFMA A operands (v_mfma_f32_4x4x1_16b_f32: the 4 rows of an XCD are the
@@ -6,6 +6,7 @@
 //
 // Shapes: hidden 896 (split 448), quantisation 256 — BASELINE config 5.
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #include "fatchord_xcd.h"
@@ -130,5 +131,9 @@ __host__ __device__ inline DxLds dx_lds_layout(bool dbg = false) {
     l.total = o;
     return l;
 }
+
+// host launchers (deepmind_xcd.hip)
+hipError_t launch_dx(const DxArgs &a, hipStream_t st);
+hipError_t prepare_dx_kernel(int max_lds_bytes, bool *ok);
 
 }  // namespace wrnn

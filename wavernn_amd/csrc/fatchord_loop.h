@@ -1,5 +1,7 @@
-// Shared between the host launcher (capi.cpp) and the device code (fatchord_loop.hip).
+// Shared between the host side (capi*.cpp) and the device code (fatchord_loop.hip).
 #pragma once
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace wrnn {
@@ -93,5 +95,13 @@ __host__ __device__ inline LdsLayout lds_layout(int slab_total, int Bc, int R, i
     l.total = o;
     return l;
 }
+
+// host launchers (fatchord_loop.hip)
+hipError_t launch_ci_gemm(const float *cond, int CD, int Bt, int b0, int Bc, int t0, int L, const float *W, int ldw,
+                          const float *bias, int N, int K, float *cI, int ldc, hipStream_t st);
+hipError_t launch_loop(const LoopArgs &a, size_t lds_bytes, hipStream_t st);
+hipError_t prepare_loop_kernel(int max_lds_bytes);
+hipError_t loop_occupancy(int *blocks_per_cu, size_t lds_bytes);
+bool loop_has_fast_path(int R, int F, int A, int NC, bool mol, int U, int UF, int UC);
 
 }  // namespace wrnn

@@ -1,6 +1,7 @@
-// Shared between the host launcher (capi.cpp) and fatchord_rows.hip: the multi-row
+// Shared between the host side (capi*.cpp) and fatchord_rows.hip: the multi-row
 // (fold-batched) variant of the sample loop.
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #include "fatchord_loop.h"
@@ -129,5 +130,14 @@ __host__ __device__ inline RowsLds rows_lds_layout(int slab_total, int B, int TB
     l.total = o;
     return l;
 }
+
+// host launchers (fatchord_rows.hip); the GEMM-input packers serve every path's terms GEMM
+hipError_t launch_pack_cond_input(const float *cond, int CD, int Bt, int b0, int B, int t0, int Lc, int KX, float *X,
+                                  hipStream_t st, int split = 0, float one = 1.0f);
+hipError_t launch_pack_terms_input(const float *cond, int CD, int Bt, int b0, int B, int t0, int Lc, int feat, int A,
+                                   int R, int KX, float *X, hipStream_t st);
+hipError_t launch_rows(const RowsArgs &a, const RowsGroup *g1, size_t lds_bytes, hipStream_t st);
+hipError_t prepare_rows_kernel(int max_lds_bytes);
+hipError_t rows_occupancy(int *blocks_per_cu, size_t lds_bytes);
 
 }  // namespace wrnn

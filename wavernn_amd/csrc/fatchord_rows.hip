@@ -9,7 +9,7 @@
 //   * grid = G workgroups (one per CU); workgroup w owns GRU units [w·U, w·U+U), fc1/fc2 rows
 //     [w·UF, …) and (RAW) fc3 rows [w·UC, …), as in the latency kernel;
 //   * every term that depends only on the conditioning (P1, P2, the conditioning part of fc1,
-//     V2) was computed for all steps by one fp32 GEMM before the launch (capi.cpp: rocBLAS),
+//     V2) was computed for all steps by one fp32 GEMM before the launch (capi_loops.cpp: rocBLAS),
 //     so a workgroup streams NT = 16 floats per row-step of its own terms;
 //   * each stage ends in a bulk hand-off (fatchord_rows.h): sc1 stores → vmcnt(0) → barrier →
 //     flag; consumers poll all G flags and LDS-DMA the rows (sc1) tile by tile;

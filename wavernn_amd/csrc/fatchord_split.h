@@ -1,6 +1,7 @@
-// Shared between the host launcher (capi.cpp) and fatchord_split.hip: the role-split latency
+// Shared between the host side (capi*.cpp) and fatchord_split.hip: the role-split latency
 // kernel for one MoL row (the BASELINE headline, batch 1).
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #include "fatchord_loop.h"
@@ -83,5 +84,11 @@ __host__ __device__ inline SplitLds split_lds_layout(int slab_total, int R, int 
     l.total = o;
     return l;
 }
+
+// host launchers (fatchord_split.hip)
+hipError_t launch_split(const SplitArgs &a, size_t lds_bytes, hipStream_t st);
+hipError_t prepare_split_kernel(int max_lds_bytes);
+hipError_t split_occupancy(int *blocks_per_cu, size_t lds_bytes);
+bool split_has_kernel(int R, int F);
 
 }  // namespace wrnn

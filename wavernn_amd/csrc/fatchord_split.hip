@@ -21,7 +21,7 @@
 // GH1 = W_hh1·h1_t → publish step t+1's GRU1 terms, gather h2_t → GH2 = W_hh2·h2_t, and
 // gather step t+1's terms of all units.  Everything that depends only on the conditioning
 // (P1 = W_ih1·cI, P2 = W_ih2·[cI; a2], V1c = W1[:, R:]·a3 + b1, V2 = W2[:, F:]·a4 + b2, and
-// cI itself) comes from one fp32 GEMM before the launch (capi.cpp) and is streamed into an LDS
+// cI itself) comes from one fp32 GEMM before the launch (capi_loops.cpp) and is streamed into an LDS
 // ring by the loader wave, so the LDS holds only the loop matrices (and, FC, 16 fc3 columns).
 //
 // Arithmetic is fp32; the sums are re-associated like fatchord_loop.hip's (tolerance-checked

@@ -1,7 +1,8 @@
-// Shared between the host launcher (capi.cpp) and fatchord_xcd.hip: the XCD-resident MoL
+// Shared between the host side (capi*.cpp) and fatchord_xcd.hip: the XCD-resident MoL
 // kernel — one utterance (row) per XCD, its whole sample loop on that XCD's 32 CUs, every
 // hand-off kept inside the XCD's L2.
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 namespace wrnn {
@@ -167,5 +168,12 @@ __host__ __device__ constexpr XcdLds xcd_lds_layout() {
     return l;
 }
 static_assert(xcd_lds_layout().total * 4 <= 160 * 1024, "the XCD kernel's LDS image fits a CU's 160 KB");
+
+// host launchers (fatchord_xcd.hip)
+hipError_t launch_xcd(const XcdArgs &a, hipStream_t st);
+hipError_t launch_xcd_group(const XcdGroupArgs &g, hipStream_t st);
+hipError_t launch_xcd_list(const XcdListArgs &g, hipStream_t st);
+hipError_t prepare_xcd_kernel(int max_lds_bytes);
+hipError_t xcd_occupancy(int *blocks_per_cu);
 
 }  // namespace wrnn

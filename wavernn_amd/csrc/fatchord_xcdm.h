@@ -1,4 +1,4 @@
-// Shared between the host launcher (capi.cpp) and fatchord_xcdm.hip: the XCD-resident MoL kernel
+// Shared between the host side (capi*.cpp) and fatchord_xcdm.hip: the XCD-resident MoL kernel
 // for MANY rows — up to 16 rows (utterances or folds) on each XCD, all of them stepping together
 // through one copy of the weights held in the XCD's 32 CUs, the matvecs on the matrix cores
 // (v_mfma_f32_4x4x1_16b_f32 at ≤ 2 quads of 4 batch rows, v_mfma_f32_16x16x4_f32 at 3–4 quads),
@@ -8,6 +8,7 @@
 // or RAW 9-bit (512 classes, fatchord_version.py:231-237): fc3 is then a twelfth 16-row set (the
 // own classes 16c..16c+15, A operands in LDS), f2 a full hop vector and the logits a sixth one.
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #include "fatchord_xcd.h"
@@ -77,7 +78,7 @@ struct XcdmSlab {
 // kernels' 160-slot record this kernel uses (compact weights d_xmWt: 32 × 144 rows)
 constexpr int kMRing = 144;
 // The terms GEMM is split into three groups so that each reads only the input columns it
-// depends on (capi.cpp, generate_xcdm: 53 % of the FLOPs of one full-depth GEMM): [P1 | cI] on
+// depends on (capi_loops.cpp, generate_xcdm: 53 % of the FLOPs of one full-depth GEMM): [P1 | cI] on
 // mel‖a1‖1, P2 on mel‖a1‖1‖a2, [V1 | V2] on a3‖a4‖1.  The record of one row-step is segmented by
 // group, workgroup-major inside each — [(P1 ‖ cI) of wg 0..31 | P2 of wg 0..31 | (V1 ‖ V2) of
 // wg 0..31] — so each group is one plain GEMM writing a contiguous row range, and a workgroup
@@ -123,7 +124,7 @@ struct XcdmArgs {
     const struct XcdmRow *rows;   // grouped launches (kGrp): [nb] per-row records in device memory, else nullptr
 };
 
-// ---- grouped launches (wide streaming sessions, capi.cpp: wide_group_launches) -----------------
+// ---- grouped launches (wide streaming sessions, capi_stream.cpp: wide_group_launches) -----------------
 // Launch row r (XCD r % 8, slot r / 8) belongs to some session at some step of its own.  The kernel
 // runs launch-local steps j = 0 .. Lc − 1 (t0 = 0: tags, slot parities and ring parities restart in
 // every launch, over a hop area the host has reset to all-ones); the row's absolute step appears
@@ -209,5 +210,15 @@ __host__ __device__ inline XcdmLds xcdm_lds_layout(int nq, bool dbg = false, boo
     l.total = o;
     return l;
 }
+
+// host launchers (fatchord_xcdm.hip): the kernel and its grouped instantiation, the Philox draws
+hipError_t launch_xcdm(const XcdmArgs &a, int nq, bool raw, hipStream_t st);
+hipError_t prepare_xcdm_kernel(int max_lds_bytes);
+hipError_t xcdm_max_quads(int max_lds_bytes, bool raw, int *nq_max);
+hipError_t launch_xcdm_group(const XcdmArgs &a, bool raw, hipStream_t st);
+hipError_t prepare_xcdm_group_kernel(int max_lds_bytes, bool raw, bool *ok);
+hipError_t launch_philox_fill(float *out, unsigned long long seed, long long row0, int nb, int t0, int Lc, int K, int mol,
+                              hipStream_t st);
+hipError_t launch_draws_wide(float *out, const XcdmRow *rows, int nb, int Lc, int K, int mol, hipStream_t st);
 
 }  // namespace wrnn

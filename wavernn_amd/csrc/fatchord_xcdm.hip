@@ -30,10 +30,10 @@
 //      producers' partials of every row and samples it itself (waves 0..3, one row each);
 //      more rows — workgroup c samples row c alone and publishes x [hop X], every workgroup
 //      gathers the x of all rows (a fifth hop instead of 32× the partial-logit traffic)
-// The conditioning terms of step t + 1 (terms GEMM, capi.cpp) and its sampler noise are loaded
+// The conditioning terms of step t + 1 (terms GEMM, capi_loops.cpp) and its sampler noise are loaded
 // by waves 4..7 after their f1 poll and stored into an LDS ring before the step's last barrier.
 //
-// Wide streaming sessions (capi.cpp: wide_group_launches) run the grouped instantiation (kGrp;
+// Wide streaming sessions (capi_stream.cpp: wide_group_launches) run the grouped instantiation (kGrp;
 // fatchord_xcdm.h: XcdmRow): launch-local steps, per-row draws / output / state from a row table.
 //
 // Membership as in fatchord_xcd.hip (XCC id + per-XCD arrival counter; bounded waits).  fp32,

@@ -1,8 +1,9 @@
-// Shared between the host launcher (capi.cpp) and fatchord_xcds.hip: the XCD-resident MoL
+// Shared between the host side (capi*.cpp) and fatchord_xcds.hip: the XCD-resident MoL
 // kernel for rnn 896 with 4×4 block-sparse GRU matrices (BASELINE config 4, pruning.py) — one
 // utterance (row) per XCD, its whole sample loop on that XCD's 32 CUs, every hand-off inside the
 // XCD's L2 (the same scheme as fatchord_xcd.h for dense rnn 512).
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #include "fatchord_xcd.h"
@@ -111,5 +112,12 @@ __host__ __device__ inline XcdsLds xcds_lds_layout() {
     l.total = o;
     return l;
 }
+
+// host launchers (fatchord_xcds.hip)
+hipError_t launch_xcds(const XcdsArgs &a, hipStream_t st);
+hipError_t launch_xcds_group(const XcdsGroupArgs &g, hipStream_t st);
+hipError_t launch_xcds_list(const XcdsListArgs &g, hipStream_t st);
+hipError_t prepare_xcds_kernel(int max_lds_bytes);
+hipError_t xcds_occupancy(int *blocks_per_cu);
 
 }  // namespace wrnn

@@ -190,7 +190,7 @@ hipError_t launch_terms_interp_win(const float *FT, int ft_base, const float *AT
     return hipGetLastError();
 }
 
-// ---- wide streaming groups (capi.cpp: wide_group_launches): the windowed pass for every row of one
+// ---- wide streaming groups (capi_stream.cpp: wide_group_launches): the windowed pass for every row of one
 // launch, from the row table (fatchord_xcdm.h: XcdmRow) — row k's frame-term stores, their bases and
 // its first step — into column k of the launch-shared record [nt][nb][N].  The stores are in the
 // many-row kernel's segmented record order already (the pass is elementwise); per sample the sum
@@ -243,7 +243,7 @@ hipError_t launch_terms_interp_wide(const XcdmRow *rows, const float *coef, floa
     return hipGetLastError();
 }
 
-// ---- folded lists (capi.cpp: wrnn_generate_list_folds): the table-driven pass for fold rows --------
+// ---- folded lists (capi_lists.cpp: wrnn_generate_list_folds): the table-driven pass for fold rows --------
 // Launch row k is one fold of some utterance: its XcdmRow gives the utterance's whole frame-term
 // stores (base 0, fr_ld floats between frame rows), its FoldRow the utterance position of launch
 // step 0 and the utterance's frame count.  A fold may start inside a frame (target + overlap need

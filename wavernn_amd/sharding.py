@@ -7,7 +7,7 @@ the rows of ONE persistent-kernel launch (`WaveRNN.generate_many`; deepmind: `ge
 Each loop row's sampler draws are keyed by its GLOBAL row id (Philox (seed, row)), so every
 utterance sees the same random draws whatever the number of GPUs.  What the GPU count does change
 is the SHAPE of each rank's launch (its row count), and with it the kernel the C-ABI picks
-(`choose_path`, capi.cpp: MoL rnn 512 runs fatchord_xcd_kernel up to 8 rows and
+(`choose_path`, capi_loops.cpp: MoL rnn 512 runs fatchord_xcd_kernel up to 8 rows and
 fatchord_xcdm_kernel from 9; RAW and deepmind one kernel at every row count) and the tiling the
 frame-rate terms GEMM gets.  So the promise is: deepmind outputs bit-identical across world sizes;
 RAW labels identical in every test so far (the terms are rounded differently, so a label exactly at
