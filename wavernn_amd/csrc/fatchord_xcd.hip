@@ -269,11 +269,12 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
     }
 
     // ---- register-resident weights: one role-indexed set of 28 float4 (chunks li + 32m of a row)
-    //   GRU2 waves (0, 5..7; group g2): W[12j + 4q + m] = W_ih2 gate q of unit 4·g2 + 2j + e (slab
-    //     pair 2·g2 + j); W[24 + m]: W_hh2 pass 7 + w (waves 5..7; wave 0: none — its F2 poll buffer
-    //     is a transient of the poll, when no GRU2 operand is live)
-    //   waves 1, 2 / 3, 4: W[0..15] fc1 / fc2 rows 8h + r, r = 0..7, at the granules this lane polls
-    //     (fc8_rows); W[16 + 4p + m]: W_hh2 passes 3(w − 1) + p, p = 0..2
+    //   GRU2 waves (0, 5..7; group g2): W_ih2 gate q of unit 4·g2 + 2j + e (slab pair 2·g2 + j) as
+    //     three row pairs interleaved for e32part2, W[8p + 0..7]: (a_r, a_z), (b_r, b_z), (a_n, b_n)
+    //     with a, b the units j = 0, 1; W[24 + m]: W_hh2 pass 7 + w (waves 5..7; wave 0: none — its
+    //     F2 poll buffer is a transient of the poll, when no GRU2 operand is live)
+    //   waves 1, 2 / 3, 4: W[0..15] fc1 / fc2 rows 8h + r, r = 0..7, at the granules this lane polls,
+    //     as four row pairs (fc8_rows_rp); W[16 + 4p + m]: W_hh2 passes 3(w − 1) + p, p = 0..2
     f4v W[28];
     auto ldrow = [&](const float *row, int m) { return *reinterpret_cast<const f4v *>(row + 4 * (li + 32 * m)); };
     const bool fcw = wave >= kXWaveFc1 && wave < kXWaveFc2 + 2;
@@ -283,30 +284,35 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
         const int hf = (wave - kXWaveFc1) & 1;
         const float *Wf = S + (wave < kXWaveFc2 ? a.s.w1 : a.s.w2) + hf * 8 * R;
 #pragma unroll
-        for (int r = 0; r < 8; ++r)
+        for (int p = 0; p < 4; ++p)
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const f2v lo = *reinterpret_cast<const f2v *>(Wf + r * R + 2 * (lane + 64 * (2 * hh)));
-                const f2v hi = *reinterpret_cast<const f2v *>(Wf + r * R + 2 * (lane + 64 * (2 * hh + 1)));
-                W[2 * r + hh] = f4v{lo.x, lo.y, hi.x, hi.y};
+            for (int kk = 0; kk < 4; ++kk) {
+                const f2v ra = *reinterpret_cast<const f2v *>(Wf + 2 * p * R + 2 * (lane + 64 * kk));
+                const f2v rb = *reinterpret_cast<const f2v *>(Wf + (2 * p + 1) * R + 2 * (lane + 64 * kk));
+                W[4 * p + kk] = f4v{ra.x, rb.x, ra.y, rb.y};
             }
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int m = 0; m < 4; ++m) W[16 + 4 * p + m] = ldrow(S + a.s.whh2 + (2 * (3 * (wave - 1) + p) + eng) * R, m);
     } else {
+        auto g2row = [&](int j, int q) { return S + a.s.wih2 + ((2 * g2 + j) * 6 + 2 * q + eng) * R; };
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int p = 0; p < 3; ++p) {
+            const float *ra = g2row(p == 1 ? 1 : 0, p == 2 ? 2 : 0), *rb = g2row(p == 0 ? 0 : 1, p == 2 ? 2 : 1);
 #pragma unroll
-            for (int q = 0; q < 3; ++q)
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    W[12 * j + 4 * q + m] = ldrow(S + a.s.wih2 + ((2 * g2 + j) * 6 + 2 * q + eng) * R, m);
+            for (int m = 0; m < 4; ++m) {
+                const f4v wa = ldrow(ra, m), wb = ldrow(rb, m);
+                W[8 * p + 2 * m] = f4v{wa.x, wb.x, wa.y, wb.y};
+                W[8 * p + 2 * m + 1] = f4v{wa.z, wb.z, wa.w, wb.w};
+            }
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m)
             W[24 + m] = wave != 0 ? ldrow(S + a.s.whh2 + (2 * (7 + wave) + eng) * R, m) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
     }
     auto W4 = [&](int i) -> const f4v(&)[4] { return *reinterpret_cast<const f4v(*)[4]>(&W[i]); };
+    auto W4x8 = [&](int i) -> const f4v(&)[8] { return *reinterpret_cast<const f4v(*)[8]>(&W[i]); };
     auto W4x16 = [&]() -> const f4v(&)[16] { return *reinterpret_cast<const f4v(*)[16]>(&W[0]); };
     // GRU1 of unit tid: x-coefficients
     const float q1r = S[a.s.q1a + tid], q1z = S[a.s.q1a + R + tid], q1n = S[a.s.q1a + 2 * R + tid];
@@ -475,7 +481,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
         bar();
         XSTAMP(1);
         // ---- GRU2 (:212-214) on waves 0, 5..7: the engine's two units, W_ih2[:, :R]·h1 of their six
-        // gate rows (each row's sum tree as e32dot's).  The four r and z rows first, reduce-scattered
+        // gate rows (two rows per packed FMA: e32part2).  The four r and z rows first, reduce-scattered
         // to lanes 0..3 of the engine (a_r, a_z, b_r, b_z), where one sigmoid pass serves all four;
         // the two n rows and their reduce (a_n → lanes 0, 1, b_n → lanes 2, 3) issue under that
         // pass's exp → rcp chain.  tanh and h' in lanes 0 and 2: r is the lane's own sigmoid, z its
@@ -489,9 +495,11 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
             float yb = xi + h1s[c * kXUnits + ui];
             uint32_t tagv = tag;
             asm volatile("" : "+v"(yb), "+v"(tagv));
-            const float g_s = e32rs4(e32part(W4(0), hx), e32part(W4(4), hx), e32part(W4(12), hx), e32part(W4(16), hx), lane);
+            const f2v ga = e32part2(W4x8(0), hx), gb = e32part2(W4x8(8), hx);
+            const float g_s = e32rs4(ga.x, ga.y, gb.x, gb.y, lane);
             const float s = sigmoid_(ghv[0] + (g_s + p2q[0]));   // lane 0: r_a, 1: z_a, 2: r_b, 3: z_b
-            const float g_n = e32rs2(e32part(W4(8), hx), e32part(W4(20), hx), lane);
+            const f2v gn = e32part2(W4x8(16), hx);
+            const float g_n = e32rs2(gn.x, gn.y, lane);
             const float z = WRNN_DPP(s, 0xF5);                   // quad_perm [1,1,3,3]
             const float n = tanh_((g_n + p2q[1]) + ghv[1] * s);
             const float hn = (h2own - n) * z + n;
@@ -511,7 +519,7 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
         //   after f1 gathered : gather h2 (wave 6), S (waves 1, 2, 5, then 4), the ring (wave 7)
         //   after h2 gathered : W_hh2·h2 (waves 1..7)
         auto pub_h2 = [&]() { pub4(XH_H2, h2own, tag); };   // GRU2 waves
-        // fc waves: lane l ends fc8_rows with row 8h + j + 2·(l >> 4) in o[j]; lanes with
+        // fc waves: lane l ends fc8_rows_rp with row 8h + j + 2·(l >> 4) in o[j]; lanes with
         // (l & 15) < 2 publish row 8h + (l & 1) + 2·(l >> 4)
         const int jq = lane & 1, rho = jq + 2 * (lane >> 4);
         if (wave == 0) {
@@ -591,11 +599,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
             xpoll16<4>(XG(XH_Y), tag, a.ctl, a.timeout_ticks, t, XH_Y, abort_flag, lane, v);
             if (hf == 0) set_flag(ygot, tag);
             XSTAMPW(3, 1);
-            f2v yk[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) yk[kk] = f2v{__uint_as_float(v[kk].x), __uint_as_float(v[kk].z)};
             float o[2];
-            fc8_rows(W4x16(), yk, o);
+            fc8_rows_rp(W4x16(), v, o);
             const float A = (jq == 0 ? o[0] : o[1]) + v1;
             if ((lane & 15) < 2) xpub_b(xgr, XGI(XH_F1) + c * kXFcRows + rg, tag, A > 0.0f ? A : 0.0f);
             XSTAMPW(4, 1);
@@ -636,11 +641,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
             xpoll16<4>(XG(XH_F1), tag, a.ctl, a.timeout_ticks, t, XH_F1, abort_flag, lane, v);
             if (hf == 0) set_flag(f1got, tag);
             XSTAMPW(5, 3);
-            f2v fk[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) fk[kk] = f2v{__uint_as_float(v[kk].x), __uint_as_float(v[kk].z)};
             float o[2];
-            fc8_rows(W4x16(), fk, o);
+            fc8_rows_rp(W4x16(), v, o);
             float p = 0.0f;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {

@@ -51,7 +51,7 @@ namespace wrnn {
 
 // 8 rows of an (NK·128)-wide layer against a vector polled into registers by ONE wave: lane l
 // holds the pairs k = 0..NK-1 at granules 2(l + 64k) + {0, 1} (xk[k]) and the matching weights
-// of row r in w[r·NK + k].  Packed FMAs, then the reduce-scatter of fc8_rows: o[j] = full sum of
+// of row r in w[r·NK + k].  Packed FMAs, then the reduce-scatter of fc8_rows_rp: o[j] = full sum of
 // row j + 2·(l >> 4), identical bits in all 16 lanes of DPP row l >> 4.
 template <int NK>
 __device__ __forceinline__ void fc8_rows_k(const f2v *w, const f2v (&xk)[NK], float (&o)[2]) {

@@ -179,18 +179,29 @@ __device__ __forceinline__ float e32dot(const f4v (&w)[4], const f4v (&x)[4]) {
     return perm_sum16(row_sum16(s.x + s.y));
 }
 
-// The in-lane part of e32dot (no cross-lane sum)
-__device__ __forceinline__ float e32part(const f4v (&w)[4], const f4v (&x)[4]) {
-    f2v a = __builtin_elementwise_fma(w[0].xy, x[0].xy, f2v{0.0f, 0.0f});
-    f2v b = __builtin_elementwise_fma(w[1].xy, x[1].xy, f2v{0.0f, 0.0f});
-    a = __builtin_elementwise_fma(w[0].zw, x[0].zw, a);
-    b = __builtin_elementwise_fma(w[1].zw, x[1].zw, b);
-    a = __builtin_elementwise_fma(w[2].xy, x[2].xy, a);
-    b = __builtin_elementwise_fma(w[3].xy, x[3].xy, b);
-    a = __builtin_elementwise_fma(w[2].zw, x[2].zw, a);
-    b = __builtin_elementwise_fma(w[3].zw, x[3].zw, b);
-    const f2v s = a + b;
-    return s.x + s.y;
+// The in-lane parts of TWO rows of an engine, packed across the rows instead of across K: w holds
+// the rows a, b interleaved — w[2m] = {a.x, b.x, a.y, b.y}, w[2m + 1] = {a.z, b.z, a.w, b.w} of
+// their chunks li + 32m — and every packed FMA multiplies one pair {a_i, b_i} by x_i in both
+// halves (an operand-select broadcast of x_i's register: no instruction).  Both halves of the
+// accumulator are a row's whole in-lane sum (.x: row a, .y: row b): no horizontal add.  Two
+// chains of 8 (chunks 0, 2 and 1, 3) merged by one packed add: a single chain of 16 measured
+// 0.016 µs/step slower (back-to-back dependent packed FMAs wait for each other), four chains
+// 0.015 slower.  The empty asm keeps x.zw a register pair of its own: as two elements of the
+// 128-bit LDS read, hipcc copies .w into a fresh register instead of selecting the pair's high half.
+__device__ __forceinline__ f2v e32part2(const f4v (&w)[8], const f4v (&x)[4]) {
+    f2v acc[2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        f2v &a = acc[m & 1];
+        const f2v lo = x[m].xy;
+        f2v hi = x[m].zw;
+        asm("" : "+v"(hi));
+        a = __builtin_elementwise_fma(w[2 * m].xy, __builtin_shufflevector(lo, lo, 0, 0), m < 2 ? f2v{0.0f, 0.0f} : a);
+        a = __builtin_elementwise_fma(w[2 * m].zw, __builtin_shufflevector(lo, lo, 1, 1), a);
+        a = __builtin_elementwise_fma(w[2 * m + 1].xy, __builtin_shufflevector(hi, hi, 0, 0), a);
+        a = __builtin_elementwise_fma(w[2 * m + 1].zw, __builtin_shufflevector(hi, hi, 1, 1), a);
+    }
+    return acc[0] + acc[1];
 }
 
 // Σ over the lanes of a residue class (lane & 3) of an engine: the other quads of the DPP row
@@ -201,11 +212,11 @@ __device__ __forceinline__ float e32rs_tail(float b) {
     return perm_sum16(b);
 }
 
-// Four e32part rows of an engine reduce-scattered over its 32 lanes: lane l keeps the rows of
+// Four rows' in-lane sums (e32part2) of an engine reduce-scattered over its 32 lanes: lane l keeps the rows of
 // its parity against l ^ 1, then row l & 3 against l ^ 2, then e32rs_tail.  Lanes li = 0..3 end
 // with the full sums of rows 0..3 — five cross-lane stages for all four.
 // Every row's sum is the tree pair (l, l ^ 1) → quad → ror 4 → ror 8 → paired DPP row over
-// e32part's in-lane sums, whichever lane of the quad keeps it: each stage adds the same two
+// the in-lane sums, whichever lane of the quad keeps it: each stage adds the same two
 // partial sums (fp32 addition commutes), and the quads meet in quad 0 in the same order.  A row
 // therefore carries the same bits from any residue class, and from e32rs2.
 __device__ __forceinline__ float e32rs4(float t0, float t1, float t2, float t3, int lane) {
@@ -338,21 +349,30 @@ __device__ __forceinline__ void xpoll16(const unsigned long long *g, uint32_t ta
 }
 
 // 8 rows of a 512-wide layer against a vector polled into registers by ONE wave (no LDS, no
-// barrier): lane l holds the pairs k = 0..3 at granules 2(l + 64k) + {0, 1} (xk[k]) and the
-// matching weights of row r in w[2r + k/2] (.xy for even k, .zw for odd).  Packed FMAs, then a
-// reduce-scatter over the wave — permlane32 swap (row r vs r + 4), permlane16 swap (r vs r + 2),
-// DPP sum over the 16 lanes of a row — leaves in o[j] the full sum of row j + 2·(l >> 4),
-// identical bits in all 16 lanes of DPP row l >> 4.
-__device__ __forceinline__ void fc8_rows(const f4v (&w)[16], const f2v (&xk)[4], float (&o)[2]) {
+// barrier), on the poll registers themselves: lane l holds the polled units v[k] = {value, tag,
+// value, tag} of granules 2(l + 64k) + {0, 1}, k = 0..3, and the weights as row pairs p = 0..3
+// (rows 2p, 2p + 1): w[4p + k] = {W[2p][i], W[2p + 1][i], W[2p][i + 1], W[2p + 1][i + 1]},
+// i = 2(l + 64k).  Every packed FMA multiplies one pair by v[k].x or v[k].z in both halves (each
+// the low register of an aligned pair: an operand-select broadcast, no instruction), so the
+// accumulator halves are the in-lane sums of rows 2p and 2p + 1 — no pairing of the polled values
+// and no horizontal add.  One chain of 8 per row pair: the four pairs interleave, and a second
+// chain per pair (+4 packed adds) measured no faster.  Then a reduce-scatter over the wave —
+// permlane32 swap (row r vs r + 4), permlane16 swap (r vs r + 2), DPP sum over the 16 lanes of a
+// row — leaves in o[j] the full sum of row j + 2·(l >> 4), identical bits in all 16 lanes of DPP
+// row l >> 4.
+__device__ __forceinline__ void fc8_rows_rp(const f4v (&w)[16], const u4v (&v)[4], float (&o)[2]) {
     float s[8];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        f2v acc = __builtin_elementwise_fma(w[2 * r].xy, xk[0], f2v{0.0f, 0.0f});
-        f2v acc2 = __builtin_elementwise_fma(w[2 * r].zw, xk[1], f2v{0.0f, 0.0f});
-        acc = __builtin_elementwise_fma(w[2 * r + 1].xy, xk[2], acc);
-        acc2 = __builtin_elementwise_fma(w[2 * r + 1].zw, xk[3], acc2);
-        const f2v t = acc + acc2;
-        s[r] = t.x + t.y;
+    for (int p = 0; p < 4; ++p) {
+        f2v acc{0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float x0 = __uint_as_float(v[k].x), x1 = __uint_as_float(v[k].z);
+            acc = __builtin_elementwise_fma(w[4 * p + k].xy, f2v{x0, x0}, acc);
+            acc = __builtin_elementwise_fma(w[4 * p + k].zw, f2v{x1, x1}, acc);
+        }
+        s[2 * p] = acc.x;
+        s[2 * p + 1] = acc.y;
     }
     float h[4];
 #pragma unroll
