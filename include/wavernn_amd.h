@@ -175,6 +175,25 @@ int wrnn_cond_shape(const wrnn_upsample_cfg *cfg, int B, int T, int target, int 
 int wrnn_upsample_pack(const wrnn_upsample_cfg *cfg, const float *mel, const float *aux, int B, int T,
                        int target, int overlap, float *cond, void *stream);
 
+/* wrnn_upsample_pack's unbatched records for a WINDOW of steps of an utterance still arriving
+ * (window addition, same ABI): steps [t0, t0 + n) of U utterances.
+ *   mel   [U][feat_dims][nm]     frames [m0, m0 + nm)      (device, fp32)
+ *   aux   [U][res_out_dims][na]  frames [a0, a0 + na)      (device, fp32)
+ *   T     the utterance's frame count, or −1 while it is unknown
+ *   cond  [n][U][feat_dims + res_out_dims]: record of step t0 + i at row i
+ * Frames outside [0, T) are zeros (pad_tensor); while T is −1 nothing lies past the end.  Every record
+ * equals, bit for bit, the one wrnn_upsample_pack writes for that step of the whole utterance: the
+ * same kernel body, the same 3-point stencil per level in the same fmaf order.
+ * WRNN_EINVAL before any launch when a window lacks a frame the steps read
+ * (wrnn_upsample_window_frames), or the steps reach past hop·T. */
+int wrnn_upsample_pack_window(const wrnn_upsample_cfg *cfg, const float *mel, int m0, int nm, const float *aux, int a0,
+                              int na, int T, int U, int t0, int n, float *cond, void *stream);
+
+/* The frames wrnn_upsample_pack_window reads for steps [t0, t0 + n) (host only, stateless): mel
+ * frames [*mel_lo, *mel_hi) and aux frames [*aux_lo, *aux_hi), clipped to [0, T) when T >= 0. */
+int wrnn_upsample_window_frames(const wrnn_upsample_cfg *cfg, int T, int t0, int n, int *mel_lo, int *mel_hi,
+                                int *aux_lo, int *aux_hi);
+
 /* wrnn_upsample_pack + wrnn_generate in one call, from the generate() inputs at FRAME rate
  * (ABI 6): mel [U][feat_dims][T] and aux [U][res_out_dims][T] (MelResNet of the padded mel) for U
  * utterances of T frames each; rows / steps as wrnn_cond_shape (target <= 0: unbatched, row u =
@@ -417,6 +436,37 @@ int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const floa
  * rnn / fc != 512, or no four-quad form of the many-row kernel on this device.  Deepmind handles
  * are refused. */
 int wrnn_stream_open_wide(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                          const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                          uint64_t seed, int64_t row_offset, wrnn_stream_t **out);
+
+/* ---- Rows sessions: streaming for any fatchord model (rows-session addition, same ABI) --------
+ * wrnn_stream_open with the same arguments, but the session runs on the multi-row kernel
+ * (wrnn_info.last_path 2; 9 when the handle streams its weights from HBM) over per-sample
+ * conditioning records, as wrnn_generate does for the models no XCD-resident kernel covers: MoL or
+ * RAW, any rnn / fc dims and class count the handle was created with.  wrnn_stream_push,
+ * wrnn_stream_plan, wrnn_stream_lookahead, wrnn_stream_mu_law and wrnn_stream_close take it like any
+ * other session: the same emission rule and look-ahead, the same argument checks and refusals, the
+ * same weight binding.  It is opt-in: wrnn_stream_open and wrnn_stream_open_wide accept and refuse
+ * what they did.
+ *   U      1 up to the rows wrnn_generate runs as ONE row block of the multi-row kernel for this
+ *          handle (at most 256; fewer when the rows' state does not fit LDS beside the weights);
+ *          WRNN_EINVAL beyond it, the message states the limit
+ *   noise  [noise_steps][U][K] by absolute step, K = 11 (MoL) or n_classes (RAW: Exp(1) draws), the
+ *          layout wrnn_generate takes; NULL: Philox keyed (seed, row_offset + u, absolute step)
+ * A push runs MelResNet on the frames whose aux became computable, writes the records of the newly
+ * runnable steps with wrnn_upsample_pack_window and runs them through wrnn_generate's own launch
+ * loop for the multi-row kernel (the same partition by row count, tile, hop form and WRNN_TERMS_MB
+ * chunking: floor(budget / (U * (terms + GEMM input))) steps per launch).  The session owns its
+ * carried state, mel / aux tails and sample window; the handle's hop areas are zeroed at the start
+ * of every push, so one-shot calls and other sessions may run between pushes in stream order.  With
+ * the same draws a session's samples are those of wrnn_generate on the whole utterance's records.
+ * A RAW session returns audio only (a label is (x + 1)·(n_classes − 1) / 2 with mu-law off).
+ * wrnn_stream_push_group refuses a rows member (WRNN_EINVAL, every member untouched): the kernel
+ * steps all rows of a launch in lock step, so a rows session advances alone.
+ * WRNN_EUNSUPPORTED (message in wrnn_last_error(h)): a deepmind handle, a handle without the
+ * multi-row kernel, a cascade that reads further ahead than pad + 1 frames, MelResNet channel counts
+ * wrnn_melresnet refuses. */
+int wrnn_stream_open_rows(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
                           const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
                           uint64_t seed, int64_t row_offset, wrnn_stream_t **out);
 

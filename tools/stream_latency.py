@@ -42,7 +42,19 @@ persistent launches per tick, × real time, and whether the N sessions are susta
 carries 8 · 275 / 22 050 s of audio, so they are when the tick's wall time stays below that.
 --raw adds leg (r) in the same invocation: leg (b) on the RAW 9-bit rnn / fc 512 model (reference
 geometry, Philox, mu-law on) — the many-row kernel's softmax head, which adds the f2 and logits hops
-to every step — and the ratio of its loop share to leg (b)'s of the same run."""
+to every step — and the ratio of its loop share to leg (b)'s of the same run.
+
+    python tools/stream_latency.py --rows rnn256 dense896 raw512 [--chunks 4 8 32] [--reps 3] [--frames 101]
+                                   [--out profiles/stream_rows_latency.jsonl]
+
+--rows MODEL... (nothing else runs): sessions on the multi-row kernel (stream(rows=True)) for models no
+XCD-resident session kernel covers — rnn256 (MoL rnn / fc 256), dense896 (MoL rnn 896, unpruned),
+raw512 (RAW 9 bits), raw10 (RAW 10 bits), mol1024 (MoL rnn 1024 / fc 768), all at the reference
+geometry.  Per model and chunk size c, total_frames announced: first audio (as above), the whole
+utterance pushed c frames at a time, µs per step (host time over frames · hop) and whether that keeps
+up with real time (1e6 / sample_rate µs per step), beside the one-shot generate() of the same utterance
+in the same run — on the path it picks by default and on the multi-row kernel (WRNN_PATH=rows).  One
+JSON line per leg, printed and appended to --out."""
 import argparse
 import json
 import os
@@ -73,23 +85,23 @@ def _timed(fn, dev):
     return out, host, e0.elapsed_time(e1)
 
 
-def first_audio(model, mel, c, known, dev):
+def first_audio(model, mel, c, known, dev, **kw):
     T = mel.shape[2]
     spec = model._upsample_spec()
     first = c + (model.pad + 1 if known else 21)
-    with model.stream(1, T if known else None, seed=1000) as s:
+    with model.stream(1, T if known else None, seed=1000, **kw) as s:
         out, host, devms = _timed(lambda: s.push(mel[:, :, :first]), dev)
     assert out.shape[1] == stream_plan(spec, first, False, T if known else None)[1] == c * model.hop_length
     return host, devms
 
 
-def total(model, mel, c, known, dev):
+def total(model, mel, c, known, dev, **kw):
     T = mel.shape[2]
     spec = model._upsample_spec()
 
     def run():
         n, launches, steps = 0, 0, 0
-        with model.stream(1, T if known else None, seed=1000) as s:
+        with model.stream(1, T if known else None, seed=1000, **kw) as s:
             for f in range(0, T, c):
                 n += s.push(mel[:, :, f:f + c]).shape[1]
                 now = stream_plan(spec, min(T, f + c), False, T if known else None)[0]
@@ -275,11 +287,75 @@ def wide_case(model, N, legs, reps, dev, d, raw_model=None):
                           "max_abs_diff": float(np.abs(audio["a"] - audio["b"]).max())}), flush=True)
 
 
+ROWS_MODELS = {
+    "rnn256": syn.FatchordDims(rnn_dims=256, fc_dims=256),
+    "dense896": syn.FatchordDims(rnn_dims=896),
+    "mol1024": syn.FatchordDims(rnn_dims=1024, fc_dims=768),
+    "raw512": syn.DEFAULT_RAW,
+    "raw10": syn.FatchordDims(bits=10, mode="RAW"),
+}
+
+
+def rows_case(name, chunks, reps, frames, dev, out_path):
+    """--rows MODEL (module docstring): one JSON line per chunk size, after the one-shot lines."""
+    med = statistics.median
+    d = ROWS_MODELS[name]
+    model = WaveRNN(**d.ctor_kwargs()).to(dev)
+    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(d, 0).items()})
+    model.eval()
+    mel = torch.from_numpy(syn.make_mel(d.feat_dims, frames, seed=1))[None].to(dev)
+    steps = frames * d.hop_length
+    real_time_us = 1e6 / d.sample_rate
+
+    def emit(row):
+        row = dict({"model": name, "mode": d.mode, "rnn_dims": d.rnn_dims, "fc_dims": d.fc_dims, "bits": d.bits,
+                    "frames": frames, "steps": steps}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        if out_path:
+            os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+            with open(out_path, "a") as f:
+                f.write(line + "\n")
+
+    def one_shot():
+        return model.generate(mel, None, False, 11000, 550, True, seed=1000, verbose=False)
+    base = {}
+    for path_env in (None, "rows"):
+        if path_env:
+            os.environ["WRNN_PATH"] = path_env
+        try:
+            one_shot()
+            runs = [_timed(one_shot, dev)[1:] for _ in range(reps)]
+            path = model.loop_handle().info["last_path"]
+        finally:
+            os.environ.pop("WRNN_PATH", None)
+        host = med(r[0] for r in runs)
+        base[path_env] = host
+        emit({"what": "one-shot generate()" + (" on the multi-row kernel (WRNN_PATH=rows)" if path_env else ""),
+              "last_path": path, "host_ms": round(host, 3), "device_ms": round(med(r[1] for r in runs), 3),
+              "us_per_step": round(host * 1e3 / steps, 3), "reps": reps})
+    for c in chunks:
+        first_audio(model, mel, c, True, dev, rows=True)
+        fa = [first_audio(model, mel, c, True, dev, rows=True) for _ in range(reps)]
+        total(model, mel, c, True, dev, rows=True)
+        tt = [total(model, mel, c, True, dev, rows=True) for _ in range(reps)]
+        host = med(t[0] for t in tt)
+        us = host * 1e3 / steps
+        emit({"what": "rows session", "last_path": model.loop_handle().info["last_path"], "chunk_frames": c,
+              "total_frames_known": True, "first_audio_frames_needed": c + model.pad + 1,
+              "first_audio_host_ms": round(med(f[0] for f in fa), 3), "first_audio_device_ms": round(med(f[1] for f in fa), 3),
+              "total_host_ms": round(host, 3), "total_device_ms": round(med(t[1] for t in tt), 3), "launches": tt[0][2],
+              "us_per_step": round(us, 3), "real_time_us_per_step": round(real_time_us, 2),
+              "x_real_time": round(real_time_us / us, 3), "real_time": bool(us < real_time_us),
+              "one_shot_host_ms": round(base[None], 3), "one_shot_rows_host_ms": round(base["rows"], 3), "reps": reps})
+    model.train()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--chunks", type=int, nargs="+", default=[4, 8, 32])
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--frames", type=int, default=401)
+    ap.add_argument("--frames", type=int, default=None, help="frames of the utterance (default 401; --rows: 101)")
     ap.add_argument("--independent", type=int, default=8, metavar="N",
                     help="sessions of the server case (1..8; 0: skip it)")
     ap.add_argument("--only-independent", action="store_true", help="skip the single-session latency rows")
@@ -289,6 +365,11 @@ def main():
                     help="--wide: a = narrow group pushes (runs on older libraries too), b = one wide group push")
     ap.add_argument("--raw", action="store_true",
                     help="--wide: add leg r, the wide leg on the RAW 9-bit rnn / fc 512 model")
+    ap.add_argument("--rows", nargs="+", choices=sorted(ROWS_MODELS), default=[], metavar="MODEL",
+                    help="only the rows-session case, for each model: " + ", ".join(sorted(ROWS_MODELS)))
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                  "stream_rows_latency.jsonl"),
+                    help="--rows: the file the JSON lines are appended to")
     args = ap.parse_args()
     if any(not 1 <= n <= 128 for n in args.wide):
         ap.error("--wide takes 1..128 sessions (a wide group has at most 128 rows)")
@@ -297,6 +378,11 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("stream_latency.py times the GPU path: no GPU visible")
     dev = torch.device("cuda", 0)
+    if args.rows:
+        for name in args.rows:
+            rows_case(name, args.chunks, args.reps, args.frames or 101, dev, args.out)
+        return
+    args.frames = args.frames or 401
     d = syn.DEFAULT_MOL
     model = WaveRNN(**d.ctor_kwargs()).to(dev)
     model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(d, 0).items()})

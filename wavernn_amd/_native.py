@@ -24,7 +24,8 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_stream_lookahead", "wrnn_stream_close", "wrnn_stream_push_group", "wrnn_fingerprint",
            "wrnn_list_plan", "wrnn_generate_list", "wrnn_stream_open_wide", "wrnn_wide_plan",
            "wrnn_stream_mu_law", "wrnn_wide_steps_per_launch", "wrnn_list_wide_plan", "wrnn_generate_list_wide",
-           "wrnn_postprocess_list", "wrnn_list_folds_plan", "wrnn_generate_list_folds", "wrnn_postprocess_list_folds")
+           "wrnn_postprocess_list", "wrnn_list_folds_plan", "wrnn_generate_list_folds", "wrnn_postprocess_list_folds",
+           "wrnn_stream_open_rows", "wrnn_upsample_pack_window", "wrnn_upsample_window_frames")
 
 
 class MelResNetCfg(ctypes.Structure):
@@ -121,6 +122,15 @@ def lib() -> ctypes.CDLL:
     L.wrnn_stream_open.restype = i32
     L.wrnn_stream_open_wide.argtypes = L.wrnn_stream_open.argtypes
     L.wrnn_stream_open_wide.restype = i32
+    L.wrnn_stream_open_rows.argtypes = L.wrnn_stream_open.argtypes
+    L.wrnn_stream_open_rows.restype = i32
+    # cfg, mel window (ptr, first frame, frames), aux window (ptr, first frame, frames), T (−1: unknown), U, t0, n, cond, stream
+    L.wrnn_upsample_pack_window.argtypes = [ctypes.POINTER(UpsampleCfg), vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp,
+                                            vp]
+    L.wrnn_upsample_pack_window.restype = i32
+    # cfg, T, t0, n → mel_lo, mel_hi, aux_lo, aux_hi
+    L.wrnn_upsample_window_frames.argtypes = [ctypes.POINTER(UpsampleCfg), i32, i32, i32, pi, pi, pi, pi]
+    L.wrnn_upsample_window_frames.restype = i32
     L.wrnn_stream_mu_law.argtypes = [vp, i32]
     L.wrnn_stream_mu_law.restype = i32
     L.wrnn_wide_steps_per_launch.argtypes = [i32, i32, i32]

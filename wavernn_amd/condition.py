@@ -14,7 +14,7 @@ No CPU fallback: the tensors must live on a GPU and the HIP library must be buil
 from __future__ import annotations
 
 import ctypes
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -150,6 +150,36 @@ def upsample_pack(spec: UpsampleSpec, mel: torch.Tensor, aux: torch.Tensor, targ
     cond = torch.empty(steps, rows, feat + spec.cfg.res_out_dims, device=mel.device, dtype=torch.float32)
     nat.check_cond(nat.lib().wrnn_upsample_pack(ctypes.byref(spec.cfg), mel.data_ptr(), aux.data_ptr(), B, T,
                                                 target, overlap, cond.data_ptr(), _stream(mel.device)))
+    return cond
+
+
+def upsample_window_frames(spec: UpsampleSpec, t0: int, n: int, total_frames: Optional[int] = None):
+    """(mel_lo, mel_hi, aux_lo, aux_hi): the mel frames [mel_lo, mel_hi) and aux frames [aux_lo, aux_hi)
+    upsample_pack_window reads for steps [t0, t0 + n) (C-ABI wrnn_upsample_window_frames, host only);
+    clipped to the utterance when total_frames is given."""
+    v = [ctypes.c_int() for _ in range(4)]
+    nat.check_cond(nat.lib().wrnn_upsample_window_frames(ctypes.byref(spec.cfg), -1 if total_frames is None else int(total_frames),
+                                                         int(t0), int(n), *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def upsample_pack_window(spec: UpsampleSpec, mel: torch.Tensor, m0: int, aux: torch.Tensor, a0: int, t0: int, n: int,
+                         total_frames: Optional[int] = None) -> torch.Tensor:
+    """upsample_pack's unbatched records for steps [t0, t0 + n) of an utterance still arriving (C-ABI
+    wrnn_upsample_pack_window): mel [U][feat][nm] holds frames [m0, m0 + nm), aux [U][res_out][na]
+    frames [a0, a0 + na); total_frames None while the end is unknown → cond [n][U][feat + res_out],
+    bit for bit the records upsample_pack writes for those steps of the whole utterance.  A window
+    that lacks a frame the steps read raises WrnnError(WRNN_EINVAL) before any launch."""
+    _need_gpu(mel, aux)
+    mel = mel.contiguous().float()
+    aux = aux.contiguous().float()
+    U, feat, nm = mel.shape
+    if feat != spec.cfg.feat_dims or aux.dim() != 3 or tuple(aux.shape[:2]) != (U, spec.cfg.res_out_dims):
+        raise ValueError(f"mel {tuple(mel.shape)} / aux {tuple(aux.shape)} do not match the upsample spec")
+    cond = torch.empty(max(int(n), 0), U, feat + spec.cfg.res_out_dims, device=mel.device, dtype=torch.float32)
+    nat.check_cond(nat.lib().wrnn_upsample_pack_window(
+        ctypes.byref(spec.cfg), mel.data_ptr(), int(m0), nm, aux.data_ptr(), int(a0), aux.shape[2],
+        -1 if total_frames is None else int(total_frames), U, int(t0), int(n), cond.data_ptr(), _stream(mel.device)))
     return cond
 
 

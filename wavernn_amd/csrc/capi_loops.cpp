@@ -46,30 +46,18 @@ int dump_stamps(wrnn_t *h, DbgBuf &dbg, size_t n, const int (&hdr)[3], hipStream
 // partition, dense weights only; WRNN_ROW_GROUPS=1|2 forces one or the other).  Measured on
 // MI355X (MoL 512, us/step, one group → two): B=2 17.2 → 15.7, B=10 18.3 → 16.9, B=32 26.6 →
 // 19.5, B=115 51.2 → 40.2: half the rows streamed per stage and half the flags per hop.
+// The per-block choices, the hop-area reset and the per-time-chunk body are wrnn::host::rows_block,
+// rows_reset and rows_chunk below: a rows session (capi_stream.cpp) runs its steps through the same.
 constexpr int kGroupRows = 2;
 constexpr size_t kRowsGranMax = 4096;   // values per row group and hop up to which hops use granules
 constexpr size_t kDmGranMax = 8192;     // the same for the deepmind kernel (one poll round of all waves)
 
 int generate_rows(wrnn_t *h, const float *cond, int B, int L, const float *noise, uint64_t seed, int64_t row_offset,
                   float *out, int32_t *labels, hipStream_t st) {
-    const wrnn_config &c = h->cfg;
-    const char *gran_env = std::getenv("WRNN_ROWS_GRANULES");
-    const int gran_force = gran_env ? std::atoi(gran_env) : -1;
-    const char *grp_env = std::getenv("WRNN_ROW_GROUPS");
-    const int grp_force = grp_env ? std::atoi(grp_env) : 0;
-    const bool can_group = h->g2.ok && !h->sparse && grp_force != 1;
-    const bool grouped = can_group && B >= 2 && (grp_force == 2 || std::min(B, kRowsMax) >= kGroupRows);
+    const bool grouped = rows_grouped(*h, B);
     PartScope ps(*h, h->g2, grouped);          // h->r*, rs, NT, d_rslab, d_Wt = the grouped partition
-    const int ng = grouped ? 2 : 1;
-    const int R = c.rnn_dims, A = c.aux_dims, N = h->rG * h->NT;
-    const size_t flag_words = (size_t)kRowsHops * kFlagSlots * kFlagStride, xr_words = (size_t)kXReps * kXRepStride;
-    if (!h->d_flags) {
-        HIP_TRY(h, hipMalloc(&h->d_flags, 2 * flag_words * 4));
-        HIP_TRY(h, hipMalloc(&h->d_xr, 2 * xr_words * 8));
-    }
+    if (int rc = rows_hop_areas(h)) return rc;
     if (int rc = blas_on(h, st)) return rc;
-    const double budget = terms_budget_floats();
-    const float one = 1.0f, zero = 0.0f;
     const char *dbg_env = std::getenv("WRNN_DEBUG_STAMPS");
     const int dbg_steps = dbg_env ? std::min(L, std::atoi(dbg_env)) : 0;
     DbgBuf dbg;
@@ -78,117 +66,31 @@ int generate_rows(wrnn_t *h, const float *cond, int B, int L, const float *noise
         HIP_TRY(h, hipMemsetAsync(dbg.p, 0, (size_t)h->rG * dbg_steps * kStamps * 4, st));
     }
     for (int b0 = 0; b0 < B;) {
-        int Bl = std::min(B - b0, kRowsMax);
-        auto group_rows = [&](int bl, int g) { const int b_0 = (bl + ng - 1) / ng; return g == 0 ? b_0 : bl - b_0; };
-        while (Bl > 1 && rows_tile_for(*h, group_rows(Bl, 0)) == 0 && rows_tile_for(*h, group_rows(Bl, 0), false) == 0) --Bl;
-        const int Bg = group_rows(Bl, 0);          // rows of group 0 (>= those of group 1)
-        // the MoL head stays in LDS while all rows fit one tile next to it; beyond that, larger
-        // tiles are worth more than an LDS-resident head (the samplers then read it from L2)
-        const bool mol = c.mode == WRNN_MODE_MOL;
-        const int tb_in = rows_tile_for(*h, Bg);
-        const bool head_lds = !mol || tb_in >= std::min(Bg, 16) || rows_tile_for(*h, Bg, false) == 0;
-        const int TB = head_lds ? tb_in : rows_tile_for(*h, Bg, false);
-        if (TB == 0) return fail(h, WRNN_EUNSUPPORTED, "rows kernel: one row of state does not fit LDS");
-        const int SW = rows_state_width(h->rU, h->rUF);
-        // GEMM input width: the composed MoL record (KXc = CD + 4) or [cI | a2 a3 a4 | 1 0 0 0]
-        // (KX); either may be the larger one (tiny dims: KXc 100 > KX 80)
-        const int KXg = rows_terms_kx(*h);
-        const int Lc_max = (int)std::max(1.0, std::min((double)L, budget / ((double)Bl * (N + KXg))));
-        const size_t T_grp = (size_t)Lc_max * Bg * N, act_grp = (size_t)kRowsHops * 2 * Bg * h->KA;
-        const size_t state_grp = (size_t)h->rG * Bg * SW + Bg;
-        if (grow(h, h->d_X, h->X_cap, (size_t)Lc_max * Bg * KXg) || grow(h, h->d_T, h->T_cap, ng * T_grp) ||
-            grow(h, h->d_act, h->act_cap, ng * act_grp) || grow(h, h->d_state, h->state_cap, ng * state_grp))
+        RowsBlock k;
+        if (int rc = rows_block(h, grouped, B - b0, L, &k)) return rc;
+        if (grow(h, h->d_X, h->X_cap, (size_t)k.Lc_max * k.Bg * k.KXg) || grow(h, h->d_T, h->T_cap, k.ng * k.T_grp) ||
+            grow(h, h->d_act, h->act_cap, k.ng * k.act_grp) || grow(h, h->d_state, h->state_cap, k.ng * k.state_grp))
             return WRNN_EHIP;
-        HIP_TRY(h, hipMemsetAsync(h->d_flags, 0, ng * flag_words * 4, st));
-        HIP_TRY(h, hipMemsetAsync(h->d_xr, 0, ng * xr_words * 8, st));
-        // granule hand-offs while a group's hop vector is small (kRowsGranMax values; measured
-        // crossover); WRNN_ROWS_GRANULES=0|1 forces bulk / granules.  The granules
-        // are zeroed per row block: tags restart at 1 with every generate()
-        const bool gran = gran_force == 1 || (gran_force != 0 && (size_t)Bg * h->KA <= kRowsGranMax);
-        const long long gstride = (((long long)Bg * h->KA + kRowsGranPad + 15) / 16) * 16;
-        // bulk mode, MoL: the f2 hop alone as granules (one hop region per group)
-        const bool f2g = !gran && mol;
-        if (gran || f2g) {
-            const size_t n = (size_t)ng * (gran ? kRowsHops : 1) * gstride;
-            HIP_TRY(h, ensure(h->d_gact, h->gact_cap, n));
-            HIP_TRY(h, hipMemsetAsync(h->d_gact, 0, n * 8, st));
+        if (int rc = rows_reset(h, k, false, st)) return rc;
+        RowsRun r{};
+        r.cond = cond;
+        r.cond_t0 = 0;
+        r.Bt = B;
+        r.b0 = b0;
+        r.noise = noise;
+        r.out = out;
+        r.out_ld = L;
+        r.labels = labels;
+        r.state = h->d_state;
+        r.seed = seed;
+        r.row_offset = row_offset;
+        for (int t0 = 0; t0 < L; t0 += k.Lc_max) {
+            const int Lc = std::min(k.Lc_max, L - t0);
+            r.dbg = (b0 == 0 && t0 == 0) ? dbg.p : nullptr;
+            r.dbg_steps = std::min(dbg_steps, Lc);
+            if (int rc = rows_chunk(h, k, r, t0, Lc, st)) return rc;
         }
-        for (int t0 = 0; t0 < L; t0 += Lc_max) {
-            const int Lc = std::min(Lc_max, L - t0);
-            // conditioning terms of steps [t0, t0 + Lc), per group: cI, then one fp32 GEMM for
-            // every workgroup's terms
-            for (int g = 0; g < ng; ++g) {
-                const int bg0 = b0 + (g ? Bg : 0), nb = group_rows(Bl, g);
-                if ((size_t)Lc * nb * KXg > h->X_cap) return fail(h, WRNN_EINVAL, "terms-GEMM input exceeds its workspace");
-                if (rows_terms_composed(*h)) {
-                    HIP_TRY(h, launch_pack_cond_input(cond, h->CD, B, bg0, nb, t0, Lc, KXg, h->d_X, st));
-                } else {
-                    HIP_TRY(h, launch_ci_gemm(cond, h->CD, B, bg0, nb, t0, Lc, h->d_IW, 1 + c.feat_dims + A, h->d_Ib, R,
-                                              c.feat_dims + A, h->d_X, h->KX, st));
-                    HIP_TRY(h, launch_pack_terms_input(cond, h->CD, B, bg0, nb, t0, Lc, c.feat_dims, A, R, h->KX, h->d_X, st));
-                }
-                if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, Lc * nb, KXg, &one,
-                                  h->d_Wt, KXg, h->d_X, KXg, &zero, h->d_T + g * T_grp, N) != rocblas_status_success)
-                    return fail(h, WRNN_EHIP, "rocblas_sgemm (conditioning terms) failed");
-            }
-            RowsArgs a{};
-            a.slab = h->d_rslab;
-            a.terms = h->d_T;
-            a.noise = noise;
-            a.out = out;
-            a.labels = labels;
-            a.act = h->d_act;
-            a.flags = h->d_flags;
-            a.xg = h->d_xr;
-            a.gact = gran ? h->d_gact : nullptr;
-            a.gstride = gstride;
-            a.gf2 = f2g ? h->d_gact : nullptr;
-            a.state = h->d_state;
-            a.ctl = h->d_ctl;
-            a.seed = seed;
-            a.row0 = row_offset + b0;
-            a.timeout_ticks = h->timeout_ticks;
-            a.L = L;
-            a.t0 = t0;
-            a.Lc = Lc;
-            a.B = Bg;
-            a.Bt = B;
-            a.b0 = b0;
-            a.R = R;
-            a.F = c.fc_dims;
-            a.A = A;
-            a.NC = c.n_classes;
-            a.NK = h->NK;
-            a.mol = c.mode == WRNN_MODE_MOL;
-            a.U = h->rU;
-            a.UF = h->rUF;
-            a.UC = h->rUC;
-            a.G = h->rG;
-            a.NT = h->NT;
-            a.TB = TB;
-            a.KA = h->KA;
-            a.s = h->rs;
-            a.dbg = (b0 == 0 && t0 == 0) ? dbg.p : nullptr;
-            a.dbg_steps = std::min(dbg_steps, Lc);
-            a.head_lds = head_lds ? 1 : 0;
-            a.gw = h->rows_gw ? 1 : 0;
-            RowsGroup g1{};
-            if (grouped) {
-                g1.terms = h->d_T + T_grp;
-                g1.act = h->d_act + act_grp;
-                g1.flags = h->d_flags + flag_words;
-                g1.xg = h->d_xr + xr_words;
-                g1.gact = gran ? h->d_gact + (size_t)kRowsHops * gstride : nullptr;
-                g1.gf2 = f2g ? h->d_gact + gstride : nullptr;
-                g1.state = h->d_state + state_grp;
-                g1.row0 = row_offset + b0 + Bg;
-                g1.B = group_rows(Bl, 1);
-                g1.b0 = b0 + Bg;
-                g1.dbg = nullptr;
-            }
-            HIP_TRY(h, launch_rows(a, grouped ? &g1 : nullptr, rows_lds_bytes(*h, Bg, TB, head_lds), st));
-        }
-        b0 += Bl;
+        b0 += k.Bl;
     }
     if (dbg.p) return dump_stamps(h, dbg, (size_t)h->rG * dbg_steps * kStamps, {h->rG, dbg_steps, kStamps}, st);
     return WRNN_OK;
@@ -706,6 +608,161 @@ namespace host {
 double terms_budget_floats() {
     const char *mb_env = std::getenv("WRNN_TERMS_MB");
     return (mb_env ? std::atof(mb_env) : 8192.0) * (1 << 20) / 4.0;
+}
+
+// ---- the multi-row kernel's launch loop in pieces (generate_rows; the rows sessions of capi_stream.cpp)
+bool rows_grouped(const wrnn_ctx &h, int B) {
+    const char *grp_env = std::getenv("WRNN_ROW_GROUPS");
+    const int grp_force = grp_env ? std::atoi(grp_env) : 0;
+    const bool can_group = h.g2.ok && !h.sparse && grp_force != 1;
+    return can_group && B >= 2 && (grp_force == 2 || std::min(B, kRowsMax) >= kGroupRows);
+}
+
+int rows_hop_areas(wrnn_t *h) {
+    const size_t flag_words = (size_t)kRowsHops * kFlagSlots * kFlagStride, xr_words = (size_t)kXReps * kXRepStride;
+    if (!h->d_flags) {
+        HIP_TRY(h, hipMalloc(&h->d_flags, 2 * flag_words * 4));
+        HIP_TRY(h, hipMalloc(&h->d_xr, 2 * xr_words * 8));
+    }
+    return WRNN_OK;
+}
+
+int rows_block(wrnn_t *h, bool grouped, int rows_left, int steps, RowsBlock *out) {
+    const wrnn_config &c = h->cfg;
+    const char *gran_env = std::getenv("WRNN_ROWS_GRANULES");
+    const int gran_force = gran_env ? std::atoi(gran_env) : -1;
+    RowsBlock k{};
+    k.ng = grouped ? 2 : 1;
+    const int ng = k.ng;
+    k.N = h->rG * h->NT;
+    int Bl = std::min(rows_left, kRowsMax);
+    auto group_rows = [&](int bl, int g) { const int b_0 = (bl + ng - 1) / ng; return g == 0 ? b_0 : bl - b_0; };
+    while (Bl > 1 && rows_tile_for(*h, group_rows(Bl, 0)) == 0 && rows_tile_for(*h, group_rows(Bl, 0), false) == 0) --Bl;
+    const int Bg = group_rows(Bl, 0);          // rows of group 0 (>= those of group 1)
+    k.Bl = Bl;
+    k.Bg = Bg;
+    k.Bg1 = group_rows(Bl, 1);
+    // the MoL head stays in LDS while all rows fit one tile next to it; beyond that, larger
+    // tiles are worth more than an LDS-resident head (the samplers then read it from L2)
+    k.mol = c.mode == WRNN_MODE_MOL;
+    const int tb_in = rows_tile_for(*h, Bg);
+    k.head_lds = !k.mol || tb_in >= std::min(Bg, 16) || rows_tile_for(*h, Bg, false) == 0;
+    k.TB = k.head_lds ? tb_in : rows_tile_for(*h, Bg, false);
+    if (k.TB == 0) return fail(h, WRNN_EUNSUPPORTED, "rows kernel: one row of state does not fit LDS");
+    k.SW = rows_state_width(h->rU, h->rUF);
+    // GEMM input width: the composed MoL record (KXc = CD + 4) or [cI | a2 a3 a4 | 1 0 0 0]
+    // (KX); either may be the larger one (tiny dims: KXc 100 > KX 80)
+    k.KXg = rows_terms_kx(*h);
+    k.Lc_max = (int)std::max(1.0, std::min((double)steps, terms_budget_floats() / ((double)Bl * (k.N + k.KXg))));
+    k.T_grp = (size_t)k.Lc_max * Bg * k.N;
+    k.act_grp = (size_t)kRowsHops * 2 * Bg * h->KA;
+    k.state_grp = (size_t)h->rG * Bg * k.SW + Bg;
+    // granule hand-offs while a group's hop vector is small (kRowsGranMax values; measured
+    // crossover); WRNN_ROWS_GRANULES=0|1 forces bulk / granules.
+    k.gran = gran_force == 1 || (gran_force != 0 && (size_t)Bg * h->KA <= kRowsGranMax);
+    k.gstride = (((long long)Bg * h->KA + kRowsGranPad + 15) / 16) * 16;
+    // bulk mode, MoL: the f2 hop alone as granules (one hop region per group)
+    k.f2g = !k.gran && k.mol;
+    *out = k;
+    return WRNN_OK;
+}
+
+// The flags, x granules and hop granules of the block's groups zeroed: tags restart at 1 with every
+// generate() (and no tag of an earlier call can satisfy a poll of a session's push).  `act`: the bulk
+// activation matrices too.
+int rows_reset(wrnn_t *h, const RowsBlock &k, bool act, hipStream_t st) {
+    const size_t flag_words = (size_t)kRowsHops * kFlagSlots * kFlagStride, xr_words = (size_t)kXReps * kXRepStride;
+    HIP_TRY(h, hipMemsetAsync(h->d_flags, 0, k.ng * flag_words * 4, st));
+    HIP_TRY(h, hipMemsetAsync(h->d_xr, 0, k.ng * xr_words * 8, st));
+    if (k.gran || k.f2g) {
+        const size_t n = (size_t)k.ng * (k.gran ? kRowsHops : 1) * k.gstride;
+        HIP_TRY(h, ensure(h->d_gact, h->gact_cap, n));
+        HIP_TRY(h, hipMemsetAsync(h->d_gact, 0, n * 8, st));
+    }
+    if (act) HIP_TRY(h, hipMemsetAsync(h->d_act, 0, k.ng * k.act_grp * sizeof(float), st));
+    return WRNN_OK;
+}
+
+// Steps [t0, t0 + Lc) of the block: the conditioning terms per group (cI or the composed record, then
+// one fp32 GEMM for every workgroup's terms) and one persistent launch.  The workspaces are grown.
+int rows_chunk(wrnn_t *h, const RowsBlock &k, const RowsRun &r, int t0, int Lc, hipStream_t st) {
+    const wrnn_config &c = h->cfg;
+    const int R = c.rnn_dims, A = c.aux_dims, N = k.N, KXg = k.KXg, Bg = k.Bg;
+    const size_t flag_words = (size_t)kRowsHops * kFlagSlots * kFlagStride, xr_words = (size_t)kXReps * kXRepStride;
+    const float one = 1.0f, zero = 0.0f;
+    const bool grouped = k.ng == 2;
+    const int tc = t0 - r.cond_t0;              // the chunk's first record in cond
+    for (int g = 0; g < k.ng; ++g) {
+        const int bg0 = r.b0 + (g ? Bg : 0), nb = g ? k.Bg1 : Bg;
+        if ((size_t)Lc * nb * KXg > h->X_cap) return fail(h, WRNN_EINVAL, "terms-GEMM input exceeds its workspace");
+        if (rows_terms_composed(*h)) {
+            HIP_TRY(h, launch_pack_cond_input(r.cond, h->CD, r.Bt, bg0, nb, tc, Lc, KXg, h->d_X, st));
+        } else {
+            HIP_TRY(h, launch_ci_gemm(r.cond, h->CD, r.Bt, bg0, nb, tc, Lc, h->d_IW, 1 + c.feat_dims + A, h->d_Ib, R,
+                                      c.feat_dims + A, h->d_X, h->KX, st));
+            HIP_TRY(h, launch_pack_terms_input(r.cond, h->CD, r.Bt, bg0, nb, tc, Lc, c.feat_dims, A, R, h->KX, h->d_X, st));
+        }
+        if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, Lc * nb, KXg, &one,
+                          h->d_Wt, KXg, h->d_X, KXg, &zero, h->d_T + g * k.T_grp, N) != rocblas_status_success)
+            return fail(h, WRNN_EHIP, "rocblas_sgemm (conditioning terms) failed");
+    }
+    RowsArgs a{};
+    a.slab = h->d_rslab;
+    a.terms = h->d_T;
+    a.noise = r.noise;
+    a.out = r.out;
+    a.labels = r.labels;
+    a.act = h->d_act;
+    a.flags = h->d_flags;
+    a.xg = h->d_xr;
+    a.gact = k.gran ? h->d_gact : nullptr;
+    a.gstride = k.gstride;
+    a.gf2 = k.f2g ? h->d_gact : nullptr;
+    a.state = r.state;
+    a.ctl = h->d_ctl;
+    a.seed = r.seed;
+    a.row0 = r.row_offset + r.b0;
+    a.timeout_ticks = h->timeout_ticks;
+    a.L = r.out_ld;
+    a.t0 = t0;
+    a.Lc = Lc;
+    a.B = Bg;
+    a.Bt = r.Bt;
+    a.b0 = r.b0;
+    a.R = R;
+    a.F = c.fc_dims;
+    a.A = A;
+    a.NC = c.n_classes;
+    a.NK = h->NK;
+    a.mol = c.mode == WRNN_MODE_MOL;
+    a.U = h->rU;
+    a.UF = h->rUF;
+    a.UC = h->rUC;
+    a.G = h->rG;
+    a.NT = h->NT;
+    a.TB = k.TB;
+    a.KA = h->KA;
+    a.s = h->rs;
+    a.dbg = r.dbg;
+    a.dbg_steps = r.dbg_steps;
+    a.head_lds = k.head_lds ? 1 : 0;
+    a.gw = h->rows_gw ? 1 : 0;
+    RowsGroup g1{};
+    if (grouped) {
+        g1.terms = h->d_T + k.T_grp;
+        g1.act = h->d_act + k.act_grp;
+        g1.flags = h->d_flags + flag_words;
+        g1.xg = h->d_xr + xr_words;
+        g1.gact = k.gran ? h->d_gact + (size_t)kRowsHops * k.gstride : nullptr;
+        g1.gf2 = k.f2g ? h->d_gact + k.gstride : nullptr;
+        g1.state = r.state + k.state_grp;
+        g1.row0 = r.row_offset + r.b0 + Bg;
+        g1.B = k.Bg1;
+        g1.b0 = r.b0 + Bg;
+        g1.dbg = nullptr;
+    }
+    HIP_TRY(h, launch_rows(a, grouped ? &g1 : nullptr, rows_lds_bytes(*h, Bg, k.TB, k.head_lds), st));
+    return WRNN_OK;
 }
 
 int blas_on(wrnn_t *h, hipStream_t st) {

@@ -1,5 +1,6 @@
 // capi_stream.cpp — streaming sessions of the C-ABI host: open / push / close, narrow groups on the
-// one-row XCD kernels, wide groups on the many-row kernel (whose launch loop the wide lists share).
+// one-row XCD kernels, wide groups on the many-row kernel (whose launch loop the wide lists share),
+// rows sessions on the multi-row kernel (any fatchord model; generate_rows' launch loop).
 #include "host_ctx.h"
 
 using namespace wrnn;
@@ -40,6 +41,7 @@ struct wrnn_stream {
     bool wide = false;              // wrnn_stream_open_wide: the many-row kernel's grouped launches (path P_XCDM)
     bool raw = false;               // a RAW handle's session (wide only): the softmax head, noise_k = kMRawNC Exp(1) draws
     bool mu_law = false;            // RAW: wrnn_stream_mu_law — the emitted samples are mu-law expanded
+    bool rows = false;              // wrnn_stream_open_rows: the multi-row kernel over per-sample records (path P_ROWS)
     int noise_k = 11;               // draws per row-step
     int U = 0, T_known = -1;
     wrnn_upsample_cfg ucfg{};
@@ -66,6 +68,12 @@ struct wrnn_stream {
     // per-push workspaces
     float *d_win = nullptr, *d_aux = nullptr, *d_frec = nullptr, *d_X = nullptr, *d_T = nullptr;
     size_t win_cap = 0, aux_cap = 0, frec_cap = 0, X_cap = 0, T_cap = 0;
+    // rows sessions: frames kept behind the newest mel / aux frame (the records of the next steps read
+    // them), the aux tail [keep][U][A4], the windows and records of a push, the layout of d_state
+    int mel_keep = 0, aux_keep = 0, atail_cur = 0, rows_ng = 0;
+    size_t rows_state_grp = 0;
+    float *d_atail[2] = {nullptr, nullptr}, *d_mwin = nullptr, *d_awin = nullptr, *d_cond = nullptr;
+    size_t mwin_cap = 0, awin_cap = 0, cond_cap = 0;
 };
 
 static int hop_of(const wrnn_upsample_cfg *c, int *hop) {
@@ -142,7 +150,8 @@ void wrnn_stream_close(wrnn_stream_t *s) {
     for (void *p : {(void *)s->d_coef, (void *)s->d_state, (void *)s->d_tail[0],
                     (void *)s->d_tail[1], (void *)s->d_xg, (void *)s->FT.buf[0], (void *)s->FT.buf[1],
                     (void *)s->AT.buf[0], (void *)s->AT.buf[1], (void *)s->d_y[0], (void *)s->d_y[1], (void *)s->d_win,
-                    (void *)s->d_aux, (void *)s->d_frec, (void *)s->d_X, (void *)s->d_T})
+                    (void *)s->d_aux, (void *)s->d_frec, (void *)s->d_X, (void *)s->d_T, (void *)s->d_atail[0],
+                    (void *)s->d_atail[1], (void *)s->d_mwin, (void *)s->d_awin, (void *)s->d_cond})
         if (p) (void)hipFree(p);   // hipFree waits for the device: no push in flight uses them
     delete s;
 }
@@ -170,28 +179,99 @@ std::string wrnn::host::wide_refusal(const wrnn_t *h) {
     return std::string();
 }
 
+// ---- rows sessions (wrnn_stream_open_rows): set-up ----------------------------------------------
+// The block generate_rows would run for the session's U rows, with the partition it picks swapped in
+// for the call only.  WRNN_OK with k->Bl < U when U rows are more than one row block.
+static int rows_session_block(wrnn_t *h, int U, int steps, RowsBlock *k) {
+    const bool grouped = rows_grouped(*h, U);
+    PartScope ps(*h, h->g2, grouped);
+    return rows_block(h, grouped, U, steps, k);
+}
+
+// Largest row count generate_rows runs as ONE row block for this handle (its rows_tile_for loop,
+// capped at kRowsMax): the tile fit only loosens with fewer rows, so the first fit from above is it
+static int rows_one_block_max(wrnn_t *h) {
+    for (int U = kRowsMax; U > 1; --U) {
+        RowsBlock k;
+        if (rows_session_block(h, U, 1, &k) == WRNN_OK && k.Bl == U) return U;
+    }
+    return 1;
+}
+
+// The frames the records of a step reach, behind and ahead, from wrnn_upsample_window_frames at a step
+// far from either end (the reach does not depend on the frame, only on the phase: a frame's first
+// step reaches furthest back, its last furthest ahead).  Ahead they must stay inside the look-ahead:
+// after R frames the session runs steps below (R − pad − 1)·hop, and those may read no frame >= R.
+static int rows_reach(wrnn_stream *s) {
+    wrnn_t *h = s->h;
+    const int q = 64, pad = s->pad, hop = s->hop;
+    int lo = 0, hi = 0, alo = 0, ahi = 0;
+    if (int rc = wrnn_upsample_window_frames(&s->ucfg, -1, q * hop, hop, &lo, &hi, &alo, &ahi))
+        return fail(h, rc, std::string("upsample window: ") + wrnn_cond_last_error());
+    if (hi > q + pad + 2)   // frame q's steps run once R = q + pad + 2 frames are in: frames [.., R)
+        return fail(h, WRNN_EUNSUPPORTED, "the upsample cascade reads " + std::to_string(hi - q - 1) + " frames ahead of a "
+                                          "step's own: more than the look-ahead of " + std::to_string(pad + 1));
+    // the oldest step of a push is (R_old − pad − 1)·hop: its frame, pad + 1 behind the newest, and the reach behind it
+    s->mel_keep = std::max(2 * pad, pad + 1 + std::max(0, q - lo));
+    s->aux_keep = 1;   // aux frames exist up to R − pad, the oldest step's own is R − pad − 1
+    return WRNN_OK;
+}
+
+static int rows_open_buffers(wrnn_stream *s) {
+    wrnn_t *h = s->h;
+    const int U = s->U, feat = h->cfg.feat_dims, A4 = h->CD - feat;
+    RowsBlock k;
+    if (int rc = rows_session_block(h, U, 1, &k)) return rc;
+    s->rows_ng = k.ng;
+    s->rows_state_grp = k.state_grp;
+    const size_t state_n = (size_t)k.ng * k.state_grp;
+    const size_t mt = (size_t)std::max(1, s->mel_keep) * U * feat, at = (size_t)s->aux_keep * U * std::max(1, A4);
+    HIP_TRY(h, hipMalloc(&s->d_state, state_n * sizeof(float)));
+    HIP_TRY(h, hipMemset(s->d_state, 0, state_n * sizeof(float)));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(h, hipMalloc(&s->d_tail[i], mt * sizeof(float)));
+        HIP_TRY(h, hipMemset(s->d_tail[i], 0, mt * sizeof(float)));
+        HIP_TRY(h, hipMalloc(&s->d_atail[i], at * sizeof(float)));
+        HIP_TRY(h, hipMemset(s->d_atail[i], 0, at * sizeof(float)));
+    }
+    HIP_TRY(h, hipDeviceSynchronize());   // the memsets are asynchronous to the host
+    return WRNN_OK;
+}
+
 static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
                        const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
-                       uint64_t seed, int64_t row_offset, wrnn_stream_t **out, bool wide) {
+                       uint64_t seed, int64_t row_offset, wrnn_stream_t **out, bool wide, bool rows = false) {
     if (!h) return WRNN_EINVAL;
     if (!out) return fail(h, WRNN_EINVAL, "need out");
     *out = nullptr;
     if (!h->ready) return fail(h, WRNN_ENOWEIGHTS, "weights not (fully) set");
     if (!ucfg || !mcfg || !melresnet_packed) return fail(h, WRNN_EINVAL, "need ucfg, mcfg and the packed MelResNet");
-    const int U_max = wide ? kMRowsMax : kXcds;
+    if (rows) {   // any fatchord handle the multi-row kernel runs, as many rows as one row block of it holds
+        if (h->dm)
+            return fail(h, WRNN_EUNSUPPORTED, "rows sessions run the fatchord multi-row kernel: this handle is a deepmind "
+                                              "one (it takes no conditioning)");
+        if (!h->rows_ok)
+            return fail(h, WRNN_EUNSUPPORTED, "rows sessions run the multi-row kernel: this handle does not have it (its "
+                                              "weights fit neither LDS nor the streamed form on this device)");
+        const int lim = rows_one_block_max(h);
+        if (U < 1 || U > lim)
+            return fail(h, WRNN_EINVAL, "a rows session has 1.." + std::to_string(lim) + " utterances (one row block of the "
+                                        "multi-row kernel for this handle), not " + std::to_string(U));
+    }
+    const int U_max = rows ? kRowsMax : wide ? kMRowsMax : kXcds;
     if (U < 1 || U > U_max) return fail(h, WRNN_EINVAL, std::string(wide ? "a wide session" : "a session") + " has 1.." +
                                                             std::to_string(U_max) + " utterances");
     if (total_frames < -1) return fail(h, WRNN_EINVAL, "total_frames is a frame count or -1");
     if (noise && noise_steps < 1) return fail(h, WRNN_EINVAL, "noise needs noise_steps >= 1");
     const bool raw = !h->dm && h->cfg.mode == WRNN_MODE_RAW;
-    if (h->dm || (h->cfg.mode != WRNN_MODE_MOL && !(raw && wide)))
+    if (h->dm || (h->cfg.mode != WRNN_MODE_MOL && !(raw && (wide || rows))))
         return fail(h, WRNN_EUNSUPPORTED, "streaming sessions run the one-row XCD MoL kernels: this handle is not MoL");
     if (wide) {
         const std::string why = wide_refusal(h);
         if (!why.empty()) return fail(h, WRNN_EUNSUPPORTED, why);
     }
-    const LoopPath path = wide ? P_XCDM : choose_path(h, U);
-    if (!wide && path != P_XCD && path != P_XCDS)
+    const LoopPath path = rows ? P_ROWS : wide ? P_XCDM : choose_path(h, U);
+    if (!wide && !rows && path != P_XCD && path != P_XCDS)
         return fail(h, WRNN_EUNSUPPORTED,
                     "streaming sessions run the dense rnn/fc 512 XCD kernel or the block-sparse rnn 896 one; " +
                         std::to_string(U) + " row(s) of this handle take loop path " + std::to_string((int)path));
@@ -207,8 +287,9 @@ static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melr
     s->loads = h->loads;
     s->path = path;
     s->wide = wide;
+    s->rows = rows;
     s->raw = raw;
-    s->noise_k = raw ? kMRawNC : 11;
+    s->noise_k = rows ? h->NK : raw ? kMRawNC : 11;
     s->U = U;
     s->T_known = total_frames;
     s->ucfg = *ucfg;
@@ -224,7 +305,12 @@ static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melr
     s->row_offset = row_offset;
     s->pad = ucfg->pad;
     std::vector<float> coef;
-    if (int rc = frame_form(h, &s->ucfg, &s->hop, &s->nJ, &s->jlo, coef)) return rc;
+    if (rows) {   // per-sample records: the cascade needs no frame-rate form, only to stay inside the look-ahead
+        if (hop_of(&s->ucfg, &s->hop)) return fail(h, WRNN_EINVAL, "bad upsample config");
+        if (int rc = rows_reach(s.get())) return rc;
+    } else if (int rc = frame_form(h, &s->ucfg, &s->hop, &s->nJ, &s->jlo, coef)) {
+        return rc;
+    }
     if (total_frames >= 0) {   // the same refusal final would give, before any work
         long long st_ = 0, au_ = 0;
         std::string msg;
@@ -232,6 +318,11 @@ static int stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melr
     }
     const int tile = wrnn_melresnet_tile_frames(mcfg, U, 1);
     if (tile < 0) return fail(h, tile, "the MelResNet kernel does not cover these channel counts");
+    if (rows) {
+        if (int rc = rows_open_buffers(s.get())) return rc;
+        *out = s.release();
+        return WRNN_OK;
+    }
     // wide: the many-row kernel's compact record and one state record per row and workgroup; its
     // launches restart their tags over the handle's hop area, so the session owns no granules
     s->N = kXcdWgs * (wide ? kMRing : path == P_XCD ? kXTerms : kSTerms);
@@ -262,6 +353,13 @@ int wrnn_stream_open(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melres
                      const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
                      uint64_t seed, int64_t row_offset, wrnn_stream_t **out) {
     return stream_open(h, ucfg, mcfg, melresnet_packed, U, total_frames, noise, noise_steps, seed, row_offset, out, false);
+}
+
+int wrnn_stream_open_rows(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const wrnn_melresnet_cfg *mcfg,
+                          const float *melresnet_packed, int U, int total_frames, const float *noise, int noise_steps,
+                          uint64_t seed, int64_t row_offset, wrnn_stream_t **out) {
+    return stream_open(h, ucfg, mcfg, melresnet_packed, U, total_frames, noise, noise_steps, seed, row_offset, out, false,
+                       true);
 }
 
 int wrnn_stream_mu_law(wrnn_stream_t *s, int on) {
@@ -366,6 +464,28 @@ static int stream_check(wrnn_stream *s, StreamPush &p) {
     return WRNN_OK;
 }
 
+// Room in the not-yet-emitted sample window for the steps up to S_new: when the live buffer is too
+// short the held-back samples move to the front of the other one, which is then the live one.
+static int stream_sample_window(wrnn_stream *s, long long S_new, hipStream_t st) {
+    wrnn_t *h = s->h;
+    const int U = s->U;
+    const int S_old = s->steps;
+    if (S_new > S_old) {
+        const int held = S_old - s->audio;   // samples run but still held back
+        if ((int)S_new - s->y_t0 > s->y_ld[s->y_cur]) {
+            const int o = 1 - s->y_cur, need = (int)S_new - s->audio;
+            if ((size_t)need * U > s->y_cap[o]) HIP_TRY(h, ensure(s->d_y[o], s->y_cap[o], (size_t)2 * need * U));
+            s->y_ld[o] = (int)(s->y_cap[o] / U);
+            if (held > 0)
+                HIP_TRY(h, hipMemcpy2DAsync(s->d_y[o], (size_t)s->y_ld[o] * 4, s->d_y[s->y_cur] + (s->audio - s->y_t0),
+                                            (size_t)s->y_ld[s->y_cur] * 4, (size_t)held * 4, U, hipMemcpyDeviceToDevice, st));
+            s->y_cur = o;
+            s->y_t0 = s->audio;
+        }
+    }
+    return WRNN_OK;
+}
+
 static int stream_prepare(wrnn_stream *s, StreamPush &p, hipStream_t st) {
     wrnn_t *h = s->h;
     const int U = s->U, feat = h->cfg.feat_dims, A4 = h->CD - feat, KX = h->KXc, N = s->N, pad = s->pad;
@@ -446,20 +566,7 @@ static int stream_prepare(wrnn_stream *s, StreamPush &p, hipStream_t st) {
         s->AT.end += Tw;
     }
     // the loop over the steps that became runnable, into the not-yet-emitted sample window
-    const int S_old = s->steps;
-    if (S_new > S_old) {
-        const int held = S_old - s->audio;   // samples run but still held back
-        if ((int)S_new - s->y_t0 > s->y_ld[s->y_cur]) {
-            const int o = 1 - s->y_cur, need = (int)S_new - s->audio;
-            if ((size_t)need * U > s->y_cap[o]) HIP_TRY(h, ensure(s->d_y[o], s->y_cap[o], (size_t)2 * need * U));
-            s->y_ld[o] = (int)(s->y_cap[o] / U);
-            if (held > 0)
-                HIP_TRY(h, hipMemcpy2DAsync(s->d_y[o], (size_t)s->y_ld[o] * 4, s->d_y[s->y_cur] + (s->audio - s->y_t0),
-                                            (size_t)s->y_ld[s->y_cur] * 4, (size_t)held * 4, U, hipMemcpyDeviceToDevice, st));
-            s->y_cur = o;
-            s->y_t0 = s->audio;
-        }
-    }
+    if (int rc = stream_sample_window(s, S_new, st)) return rc;
     p.R_new = R_new;
     p.A_new = A_new;
     return WRNN_OK;
@@ -480,6 +587,112 @@ static int stream_finish(wrnn_stream *s, const StreamPush &p, int *n_out, hipStr
     s->fin = p.final;
     s->dead = false;
     if (n_out) *n_out = p.m;
+    return WRNN_OK;
+}
+
+// ---- rows sessions: a push -----------------------------------------------------------------------
+// Refused before anything is queued: the session's rows must still be one row block of the partition
+// its carried state was laid out for (WRNN_ROW_GROUPS / WRNN_ROWS_GRANULES are read at every call)
+static int rows_check(wrnn_stream *s) {
+    wrnn_t *h = s->h;
+    RowsBlock k;
+    if (int rc = rows_session_block(h, s->U, 1, &k)) return rc;
+    if (k.Bl != s->U || k.ng != s->rows_ng || k.state_grp != s->rows_state_grp)
+        return fail(h, WRNN_EINVAL, "the multi-row kernel's partition for this session's rows changed since it was opened "
+                                    "(WRNN_ROW_GROUPS): its carried state has the other layout");
+    return WRNN_OK;
+}
+
+// stream_prepare for a rows session: the mel tail and the new frames, MelResNet on the frames whose
+// aux became computable, the aux frames the steps still to run read, then the per-sample records of
+// the newly runnable steps [S_old, S_new) (wrnn_upsample_pack_window) and room for their samples.
+static int rows_prepare(wrnn_stream *s, StreamPush &p, hipStream_t st) {
+    wrnn_t *h = s->h;
+    const int U = s->U, feat = h->cfg.feat_dims, A4 = h->CD - feat, pad = s->pad, n = p.n;
+    s->dead = true;   // as stream_prepare: from here on the session's stores advance
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int R_old = s->R, R_new = R_old + n, A_old = s->A;
+    const int A_new = p.final ? R_new : std::max(A_old, R_new - pad);
+    const int Tw = A_new - A_old, wn = Tw > 0 ? Tw + 2 * pad : 0;
+    const int S_old = s->steps, ns = (int)p.S_new - S_old;
+    const int T = p.final ? R_new : s->T_known;
+    int mlo = 0, mhi = 0, alo = 0, ahi = 0;
+    if (ns > 0) {
+        if (int rc = wrnn_upsample_window_frames(&s->ucfg, T, S_old, ns, &mlo, &mhi, &alo, &ahi))
+            return fail(h, rc, std::string("upsample window: ") + wrnn_cond_last_error());
+        if (mhi > R_new || (mhi > mlo && mlo < R_old - s->mel_keep) || ahi > A_new || alo < A_old - s->aux_keep)
+            return fail(h, WRNN_EINVAL, "rows session: the steps of this push read frames the session does not hold");
+    }
+    const int nm = mhi - mlo, na = ahi - alo;
+    if (n > 0 || Tw > 0 || ns > 0) {
+        // both windows come from the same tail and the same new frames, and leave the same new tail
+        HIP_TRY(h, ensure(s->d_win, s->win_cap, (size_t)std::max(1, wn) * U * feat));
+        HIP_TRY(h, ensure(s->d_mwin, s->mwin_cap, (size_t)std::max(1, nm) * U * feat));
+        HIP_TRY(h, launch_stream_mel_window(s->d_tail[s->tail_cur], p.mel, U, feat, n, R_old, s->mel_keep, A_old - pad, wn,
+                                            s->d_win, s->d_tail[1 - s->tail_cur], st));
+        if (nm > 0)
+            HIP_TRY(h, launch_stream_mel_window(s->d_tail[s->tail_cur], p.mel, U, feat, n, R_old, s->mel_keep, mlo, nm,
+                                                s->d_mwin, s->d_tail[1 - s->tail_cur], st));
+        s->tail_cur = 1 - s->tail_cur;
+    }
+    if (Tw > 0) {
+        HIP_TRY(h, ensure(s->d_aux, s->aux_cap, (size_t)U * A4 * Tw));
+        if (int rc = wrnn_melresnet(&s->mcfg, s->mr_packed, s->d_win, U, Tw, s->d_aux, st))
+            return fail(h, rc, std::string("wrnn_melresnet: ") + wrnn_cond_last_error());
+    }
+    if (Tw > 0 || na > 0) {   // the aux window of the steps, and the aux tail behind the newest frame
+        HIP_TRY(h, ensure(s->d_awin, s->awin_cap, (size_t)std::max(1, na) * U * A4));
+        HIP_TRY(h, launch_stream_mel_window(s->d_atail[s->atail_cur], s->d_aux, U, A4, Tw, A_old, s->aux_keep, alo, na,
+                                            s->d_awin, s->d_atail[1 - s->atail_cur], st));
+        s->atail_cur = 1 - s->atail_cur;
+    }
+    if (ns > 0) {
+        HIP_TRY(h, ensure(s->d_cond, s->cond_cap, (size_t)ns * U * h->CD));
+        if (int rc = wrnn_upsample_pack_window(&s->ucfg, s->d_mwin, mlo, nm, s->d_awin, alo, na, T, U, S_old, ns, s->d_cond, st))
+            return fail(h, rc, std::string("upsample_pack_window: ") + wrnn_cond_last_error());
+    }
+    if (int rc = stream_sample_window(s, p.S_new, st)) return rc;
+    p.R_new = R_new;
+    p.A_new = A_new;
+    return WRNN_OK;
+}
+
+// The steps [S_old, S_new) through generate_rows' own pieces: the same block choices for the
+// session's rows, the hop areas zeroed once per push, one terms GEMM and one persistent launch per
+// time chunk.  State, records and sample window are the session's; t0 is the absolute step.
+static int rows_launches(wrnn_stream *s, const StreamPush &p, hipStream_t st) {
+    wrnn_t *h = s->h;
+    const int ns = (int)p.S_new - p.S_old;
+    const bool grouped = rows_grouped(*h, s->U);
+    PartScope ps(*h, h->g2, grouped);
+    if (int rc = rows_hop_areas(h)) return rc;
+    if (int rc = blas_on(h, st)) return rc;
+    RowsBlock k;
+    if (int rc = rows_block(h, grouped, s->U, ns, &k)) return rc;
+    if (k.Bl != s->U || k.ng != s->rows_ng || k.state_grp != s->rows_state_grp)
+        return fail(h, WRNN_EINVAL, "rows session: the partition changed during the push");
+    if (grow(h, h->d_X, h->X_cap, (size_t)k.Lc_max * k.Bg * k.KXg) || grow(h, h->d_T, h->T_cap, k.ng * k.T_grp) ||
+        grow(h, h->d_act, h->act_cap, k.ng * k.act_grp))
+        return WRNN_EHIP;
+    // the handle's hop areas carry step tags: whatever a one-shot call or another session left there
+    // since the last push must not satisfy a poll of this one
+    if (int rc = rows_reset(h, k, true, st)) return rc;
+    h->last_path = h->rows_gw ? 9 : (int)P_ROWS;
+    RowsRun r{};
+    r.cond = s->d_cond;
+    r.cond_t0 = p.S_old;
+    r.Bt = s->U;
+    r.b0 = 0;
+    r.noise = s->noise;
+    // the kernel writes row b, step t at out[b·out_ld + t]: column t − y_t0 of the session's window
+    r.out = s->d_y[s->y_cur] - s->y_t0;
+    r.out_ld = s->y_ld[s->y_cur];
+    r.labels = nullptr;
+    r.state = s->d_state;
+    r.seed = s->seed;
+    r.row_offset = s->row_offset;
+    for (int t0 = p.S_old; t0 < (int)p.S_new; t0 += k.Lc_max)
+        if (int rc = rows_chunk(h, k, r, t0, std::min(k.Lc_max, (int)p.S_new - t0), st)) return rc;
     return WRNN_OK;
 }
 
@@ -680,12 +893,18 @@ int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, doubl
     StreamPush p;
     p.mel = mel, p.n = n, p.final = final != 0, p.wave = wave, p.cap = cap;
     if (int rc = stream_check(s, p)) return rc;
-    if (int rc = stream_prepare(s, p, st)) return rc;
+    if (s->rows) {
+        if (int rc = rows_check(s)) return rc;
+        if (int rc = rows_prepare(s, p, st)) return rc;
+    } else if (int rc = stream_prepare(s, p, st)) {
+        return rc;
+    }
     if (p.S_new > p.S_old) {
         HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
         h->last_path = (int)s->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
         int rc;
-        if (s->wide) rc = wide_group_launches(h, &s, &p, 1, st);
+        if (s->rows) rc = rows_launches(s, p, st);
+        else if (s->wide) rc = wide_group_launches(h, &s, &p, 1, st);
         else if (s->path == P_XCD) rc = stream_launches<XcdArgs>(s, p.S_old, (int)p.S_new, p.final, h->xs, launch_xcd, st);
         else rc = stream_launches<XcdsArgs>(s, p.S_old, (int)p.S_new, p.final, h->xss, launch_xcds, st);
         if (rc) return rc;
@@ -778,6 +997,9 @@ int wrnn_stream_push_group(wrnn_stream_t *const *sessions, int count, const floa
         for (int j = 0; j < i; ++j)
             if (sessions[j] == sessions[i])
                 return fail(h, WRNN_EINVAL, "members " + std::to_string(j) + " and " + std::to_string(i) + " are the same session");
+        if (sessions[i]->rows)
+            return fail(h, WRNN_EINVAL, "member " + std::to_string(i) + ": a rows session advances alone: its kernel steps "
+                                        "all rows in lock step");
         if (sessions[i]->path != sessions[0]->path)
             return fail(h, WRNN_EINVAL, "member " + std::to_string(i) + " runs another loop kernel than member 0");
         rows += sessions[i]->U;

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <climits>
 #include <string>
 
 #include "wavernn_amd.h"
@@ -40,13 +42,23 @@ struct UpArgs {
     //   out[s·m + φ] = Σ_d pw[φ][d] · in[m − 1 + d],  pw[φ][d] = Σ_{j : ⌊(φ+j)/s⌋ = d} w[j]
     // (in[] = 0 outside [0, N), exactly the conv's zero padding of the stretched sequence)
     float pw[kUpMaxScales][3 * kUpMaxScale];
+    // window form (upsample_pack_kernel<VEC, true>, wrnn_upsample_pack_window): steps [p0, L) of an
+    // utterance still arriving, record of step p at cond row p − p0 (nf = 1); mel holds frames
+    // [m0, m0 + mel_ld) and aux frames [a0, a0 + aux_ld); T and N[] are INT_MAX while the total is unknown
+    int p0, m0, mel_ld, a0, aux_ld;
 };
 
 // VEC: feat and A4 multiples of 4 — a lane produces 4 consecutive columns, 16-B stores
-template <bool VEC>
+// WIN: the window form (UpArgs::p0 ...): tiles start at step p0, the frames come from windows of the
+// mel and the aux, the records go to row p − p0.  Which tile a step falls into decides only what is
+// staged, never a value: every level is the same 3-point fmaf chain over the same inputs, so a
+// record's bits are those of the whole-utterance launch.
+template <bool VEC, bool WIN>
 __global__ __launch_bounds__(kUpThreads) void upsample_pack_kernel(UpArgs a) {
     extern __shared__ float lvl[];
-    const int t0 = blockIdx.x * kUpTile, t1 = min(t0 + kUpTile, a.Lp), b = blockIdx.y;
+    const int t0 = blockIdx.x * kUpTile + (WIN ? a.p0 : 0), t1 = min(t0 + kUpTile, a.Lp), b = blockIdx.y;
+    const int mel_ld = WIN ? a.mel_ld : a.T, aux_ld = WIN ? a.aux_ld : a.T;   // frames per channel row
+    const int m0 = WIN ? a.m0 : 0, a0 = WIN ? a.a0 : 0, p0 = WIN ? a.p0 : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int kWaves = kUpThreads / 64;
     const int tv = min(t1, a.L);             // steps [t0, tv) carry signal, [tv, t1) fold padding
@@ -68,10 +80,10 @@ __global__ __launch_bounds__(kUpThreads) void upsample_pack_kernel(UpArgs a) {
             const int tt = u - a.pad;
             for (int c = lane; c < feat; c += 64)
                 lvl[a.off[0] + (u - lo[0]) * feat + c] =
-                    (tt >= 0 && tt < a.T) ? a.mel[((size_t)b * feat + c) * a.T + tt] : 0.0f;
+                    (tt >= 0 && tt < a.T) ? a.mel[((size_t)b * feat + c) * mel_ld + (tt - m0)] : 0.0f;
         }
         for (int f = f0 + wave; f <= (tv - 1) / a.hop; f += kWaves)
-            for (int c = lane; c < A4; c += 64) auxs[(f - f0) * A4 + c] = a.aux[((size_t)b * A4 + c) * a.T + f];
+            for (int c = lane; c < A4; c += 64) auxs[(f - f0) * A4 + c] = a.aux[((size_t)b * A4 + c) * aux_ld + (f - a0)];
         __syncthreads();
         // levels 1 .. n-1 (:71-79)
         for (int i = 1; i < n; ++i) {
@@ -133,7 +145,7 @@ __global__ __launch_bounds__(kUpThreads) void upsample_pack_kernel(UpArgs a) {
                     }
                 }
                 for (int f = max(fh - 1, 0); f <= fh; ++f) {
-                    const int tt = p - f * a.stride;
+                    const int tt = p - f * a.stride - p0;
                     if (tt >= 0 && tt < a.win)
                         *reinterpret_cast<float4 *>(a.cond + ((size_t)tt * Bo + (size_t)b * a.nf + f) * CD + c) = v;
                 }
@@ -152,7 +164,7 @@ __global__ __launch_bounds__(kUpThreads) void upsample_pack_kernel(UpArgs a) {
                     }
                 }
                 for (int f = max(fh - 1, 0); f <= fh; ++f) {
-                    const int tt = p - f * a.stride;
+                    const int tt = p - f * a.stride - p0;
                     if (tt >= 0 && tt < a.win) a.cond[((size_t)tt * Bo + (size_t)b * a.nf + f) * CD + c] = v;
                 }
             }
@@ -405,6 +417,102 @@ int check_up(const wrnn_upsample_cfg *c) {
     if (c->feat_dims < 1 || c->res_out_dims < 0 || c->pad < 0) return cond_fail(WRNN_EINVAL, "bad dims");
     return WRNN_OK;
 }
+
+// The cascade of `cfg` over T frames into the launch arguments: scales, hop, indent, level lengths
+// (INT_MAX while T < 0: nothing lies past an end that is not known), the per-phase stencil weights.
+void up_cascade(const wrnn_upsample_cfg *cfg, int T, UpArgs &a) {
+    a.T = T < 0 ? INT_MAX : T;
+    a.feat = cfg->feat_dims;
+    a.A4 = cfg->res_out_dims;
+    a.CD = a.feat + a.A4;
+    a.pad = cfg->pad;
+    a.n_scales = cfg->n_scales;
+    a.hop = 1;
+    a.N[0] = T < 0 ? INT_MAX : T + 2 * cfg->pad;
+    for (int i = 0; i < a.n_scales; ++i) {
+        const int s = cfg->scales[i];
+        a.scales[i] = s;
+        a.hop *= s;
+        a.N[i + 1] = T < 0 ? INT_MAX : a.N[i] * s;
+        // taps (host) → per-phase 3-point stencil weights, summed in double
+        for (int ph = 0; ph < s; ++ph) {
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int j = 0; j < 2 * s + 1; ++j) acc[(ph + j) / s] += (double)cfg->taps[i][j];
+            for (int d = 0; d < 3; ++d) a.pw[i][3 * ph + d] = (float)acc[d];
+        }
+    }
+    a.indent = cfg->pad * a.hop;
+}
+
+// LDS layout of a tile, then one workgroup per tile of the `steps` steps from the launch's first
+template <bool WIN>
+int up_launch(UpArgs &a, int steps, hipStream_t st) {
+    // LDS rows per level: m rows of level i need <= m / s_i + 4 rows of level i-1
+    int cap[kUpMaxScales], m = kUpTile, off = 0;
+    for (int i = a.n_scales; i >= 1; --i) {
+        m = m / a.scales[i - 1] + 5;
+        cap[i - 1] = m;
+    }
+    for (int i = 0; i < a.n_scales; ++i) {
+        a.off[i] = off;
+        off += cap[i] * a.feat;
+    }
+    a.off[a.n_scales] = off;                       // aux frames of the tile
+    off += (kUpTile / a.hop + 2) * a.A4;
+    const size_t lds = (size_t)off * 4;
+    if (lds > 160 * 1024) return cond_fail(WRNN_EUNSUPPORTED, "upsample tile exceeds LDS");
+    const bool vec = a.feat % 4 == 0 && a.A4 % 4 == 0;
+    const void *kern = vec ? (const void *)upsample_pack_kernel<true, WIN> : (const void *)upsample_pack_kernel<false, WIN>;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return cond_fail(WRNN_EHIP, hipGetErrorString(e));
+    }
+    const dim3 grid((steps + kUpTile - 1) / kUpTile, a.B);
+    if (vec) hipLaunchKernelGGL((upsample_pack_kernel<true, WIN>), grid, dim3(kUpThreads), lds, st, a);
+    else hipLaunchKernelGGL((upsample_pack_kernel<false, WIN>), grid, dim3(kUpThreads), lds, st, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WRNN_OK : cond_fail(WRNN_EHIP, hipGetErrorString(e));
+}
+
+// The window form's arguments for steps [t0, t0 + n) of an utterance of T frames (−1: unknown)
+int up_window(const wrnn_upsample_cfg *cfg, int T, int t0, int n, UpArgs &a) {
+    if (T < -1 || t0 < 0 || n < 1) return cond_fail(WRNN_EINVAL, "need T >= -1, t0 >= 0 and n >= 1");
+    long long hop = 1;
+    for (int i = 0; i < cfg->n_scales; ++i) hop *= cfg->scales[i];
+    const long long end = (long long)t0 + n;
+    if (end + cfg->pad * hop > (1LL << 30) || (T >= 0 && hop * T > (1LL << 30)))
+        return cond_fail(WRNN_EINVAL, "utterance too long");
+    if (T >= 0 && end > hop * T)
+        return cond_fail(WRNN_EINVAL, "steps past the utterance's " + std::to_string(hop * T));
+    up_cascade(cfg, T, a);
+    a.p0 = t0;
+    a.L = a.Lp = (int)end;
+    a.nf = 1;
+    a.stride = a.L;
+    a.win = n;
+    return WRNN_OK;
+}
+
+// Frames the window form's launch stages: the lo / hi derivation of upsample_pack_kernel over the
+// whole window.  Both bounds are monotone in the step, so every tile's rows lie inside these; level-0
+// row u is mel frame u − pad, and only frames inside [0, T) are loaded (the others are zeros).
+struct UpFrames {
+    int mel_lo, mel_hi, aux_lo, aux_hi;
+};
+UpFrames up_window_frames(const UpArgs &a) {
+    int lo = a.p0 + a.indent, hi = a.L + a.indent;
+    for (int i = a.n_scales; i >= 1; --i) {
+        const int s = a.scales[i - 1];
+        lo = std::max(lo / s - 1, 0);
+        hi = std::min(a.N[i - 1], (hi - 1) / s + 2);
+    }
+    UpFrames f;
+    f.mel_lo = std::max(lo - a.pad, 0);
+    f.mel_hi = std::max(f.mel_lo, std::min(hi - a.pad, a.T));
+    f.aux_lo = a.p0 / a.hop;
+    f.aux_hi = (a.L - 1) / a.hop + 1;
+    return f;
+}
 }  // namespace
 
 }  // namespace wrnn
@@ -440,54 +548,53 @@ int wrnn_upsample_pack(const wrnn_upsample_cfg *cfg, const float *mel, const flo
     a.aux = aux;
     a.cond = cond;
     a.B = B;
-    a.T = T;
-    a.feat = cfg->feat_dims;
-    a.A4 = cfg->res_out_dims;
-    a.CD = a.feat + a.A4;
-    a.pad = cfg->pad;
-    a.n_scales = cfg->n_scales;
-    a.hop = 1;
-    a.N[0] = T + 2 * cfg->pad;
-    for (int i = 0; i < a.n_scales; ++i) {
-        const int s = cfg->scales[i];
-        a.scales[i] = s;
-        a.hop *= s;
-        a.N[i + 1] = a.N[i] * s;
-        // taps (host) → per-phase 3-point stencil weights, summed in double
-        for (int ph = 0; ph < s; ++ph) {
-            double acc[3] = {0.0, 0.0, 0.0};
-            for (int j = 0; j < 2 * s + 1; ++j) acc[(ph + j) / s] += (double)cfg->taps[i][j];
-            for (int d = 0; d < 3; ++d) a.pw[i][3 * ph + d] = (float)acc[d];
-        }
-    }
-    a.indent = cfg->pad * a.hop;
+    up_cascade(cfg, T, a);
     a.L = a.hop * T;
     fold_geometry(a.L, target, overlap, &a.nf, &a.stride, &a.win, &a.Lp);
-    // LDS rows per level: m rows of level i need <= m / s_i + 4 rows of level i-1
-    int cap[kUpMaxScales], m = kUpTile, off = 0;
-    for (int i = a.n_scales; i >= 1; --i) {
-        m = m / a.scales[i - 1] + 5;
-        cap[i - 1] = m;
-    }
-    for (int i = 0; i < a.n_scales; ++i) {
-        a.off[i] = off;
-        off += cap[i] * a.feat;
-    }
-    a.off[a.n_scales] = off;                       // aux frames of the tile
-    off += (kUpTile / a.hop + 2) * a.A4;
-    const size_t lds = (size_t)off * 4;
-    if (lds > 160 * 1024) return cond_fail(WRNN_EUNSUPPORTED, "upsample tile exceeds LDS");
-    const bool vec = a.feat % 4 == 0 && a.A4 % 4 == 0;
-    const void *kern = vec ? (const void *)upsample_pack_kernel<true> : (const void *)upsample_pack_kernel<false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return cond_fail(WRNN_EHIP, hipGetErrorString(e));
-    }
-    const dim3 grid((a.Lp + kUpTile - 1) / kUpTile, B);
-    if (vec) hipLaunchKernelGGL(upsample_pack_kernel<true>, grid, dim3(kUpThreads), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(upsample_pack_kernel<false>, grid, dim3(kUpThreads), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WRNN_OK : cond_fail(WRNN_EHIP, hipGetErrorString(e));
+    return up_launch<false>(a, a.Lp, (hipStream_t)stream);
+}
+
+int wrnn_upsample_window_frames(const wrnn_upsample_cfg *cfg, int T, int t0, int n, int *mel_lo, int *mel_hi,
+                                int *aux_lo, int *aux_hi) {
+    using namespace wrnn;
+    if (int rc = check_up(cfg)) return rc;
+    UpArgs a{};
+    if (int rc = up_window(cfg, T, t0, n, a)) return rc;
+    const UpFrames f = up_window_frames(a);
+    if (mel_lo) *mel_lo = f.mel_lo;
+    if (mel_hi) *mel_hi = f.mel_hi;
+    if (aux_lo) *aux_lo = f.aux_lo;
+    if (aux_hi) *aux_hi = f.aux_hi;
+    return WRNN_OK;
+}
+
+int wrnn_upsample_pack_window(const wrnn_upsample_cfg *cfg, const float *mel, int m0, int nm, const float *aux, int a0,
+                              int na, int T, int U, int t0, int n, float *cond, void *stream) {
+    using namespace wrnn;
+    if (int rc = check_up(cfg)) return rc;
+    if (U < 1) return cond_fail(WRNN_EINVAL, "U must be >= 1");
+    UpArgs a{};
+    if (int rc = up_window(cfg, T, t0, n, a)) return rc;
+    if (nm < 0 || na < 0 || !cond || (nm > 0 && !mel) || (na > 0 && !aux)) return cond_fail(WRNN_EINVAL, "null tensor");
+    // every frame the launch stages lies in the windows: refused here, before anything is queued
+    const UpFrames f = up_window_frames(a);
+    if (f.mel_hi > f.mel_lo && (f.mel_lo < m0 || f.mel_hi > (long long)m0 + nm))
+        return cond_fail(WRNN_EINVAL, "steps [" + std::to_string(t0) + ", " + std::to_string(t0 + n) + ") read mel frames [" +
+                                          std::to_string(f.mel_lo) + ", " + std::to_string(f.mel_hi) + "): the window holds [" +
+                                          std::to_string(m0) + ", " + std::to_string((long long)m0 + nm) + ")");
+    if (a.A4 > 0 && (f.aux_lo < a0 || f.aux_hi > (long long)a0 + na))
+        return cond_fail(WRNN_EINVAL, "steps [" + std::to_string(t0) + ", " + std::to_string(t0 + n) + ") read aux frames [" +
+                                          std::to_string(f.aux_lo) + ", " + std::to_string(f.aux_hi) + "): the window holds [" +
+                                          std::to_string(a0) + ", " + std::to_string((long long)a0 + na) + ")");
+    a.mel = mel;
+    a.aux = aux;
+    a.cond = cond;
+    a.B = U;
+    a.m0 = m0;
+    a.mel_ld = nm;
+    a.a0 = a0;
+    a.aux_ld = na;
+    return up_launch<true>(a, n, (hipStream_t)stream);
 }
 
 int wrnn_postprocess(const float *y, int rows, int steps, int batched, int overlap, int mu_law, int n_classes,

@@ -279,6 +279,36 @@ int upload_coef(wrnn_t *h, const std::vector<float> &coef, hipStream_t st);
 // The loop path for B rows (WRNN_PATH=xcd|xcdm|split|latency|rows forces one: tests, benchmarks).
 enum LoopPath { P_LATENCY = 1, P_ROWS = 2, P_DM = 3, P_SPLIT = 4, P_XCD = 5, P_XCDS = 6, P_XCDM = 7, P_DX = 8 };
 LoopPath choose_path(const wrnn_t *h, int B);
+// The multi-row kernel's launch loop in pieces, shared by generate_rows and the rows sessions
+// (capi_stream.cpp).  The caller holds the PartScope of rows_grouped(h, B) around all of them.
+// RowsBlock: what generate_rows decides per row block — the one- or two-group partition by row count,
+// tile size and head_lds, granule or bulk hops, the steps per launch under WRNN_TERMS_MB.
+struct RowsBlock {
+    int ng, Bl, Bg, Bg1;          // row groups; rows of the block, of group 0 and of group 1
+    int N, KXg, TB, SW, Lc_max;
+    bool mol, head_lds, gran, f2g;
+    long long gstride;
+    size_t T_grp, act_grp, state_grp;   // floats per group of the terms, the bulk activations, the carried state
+};
+// What a launch reads and writes: cond [..][Bt][CD] whose first record is step cond_t0, rows
+// [b0, b0 + Bl) of it; noise [steps][Bt][NK] by absolute step or nullptr (Philox); sample of row b and
+// step t at out[(b0 + b)·out_ld + t] (labels likewise, or nullptr); state [ng][state_grp] carried
+// from launch to launch (read when t0 > 0)
+struct RowsRun {
+    const float *cond, *noise;
+    float *out, *state;
+    int32_t *labels;
+    int cond_t0, Bt, b0, out_ld;
+    uint64_t seed;
+    int64_t row_offset;
+    unsigned *dbg;
+    int dbg_steps;
+};
+bool rows_grouped(const wrnn_ctx &h, int B);
+int rows_hop_areas(wrnn_t *h);
+int rows_block(wrnn_t *h, bool grouped, int rows_left, int steps, RowsBlock *out);
+int rows_reset(wrnn_t *h, const RowsBlock &k, bool act, hipStream_t st);
+int rows_chunk(wrnn_t *h, const RowsBlock &k, const RowsRun &r, int t0, int Lc, hipStream_t st);
 // The upsample config of a call against the handle's feat / aux dims, and its 1..4 scales with a
 // scale and taps each (h may be null there: no message is kept)
 int check_upsample_dims(wrnn_t *h, const wrnn_upsample_cfg *ucfg);

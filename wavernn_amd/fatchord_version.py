@@ -553,7 +553,7 @@ class WaveRNN(nn.Module):
     # --------------------------------------------------------------------- streaming
     def stream(self, n_streams: int = 1, total_frames: Optional[int] = None, *, noise=None,
                seed: Optional[int] = None, row_offset: int = 0, wide: bool = False,
-               mu_law: bool = True) -> "WaveRNNStream":
+               mu_law: bool = True, rows: bool = False) -> "WaveRNNStream":
         """A streaming session: push mel frames as the acoustic model produces them, get the audio
         that has become final — unbatched MoL generate() in pieces, the recurrent state kept on the
         GPU between pushes (C-ABI wrnn_stream_*).  `n_streams` utterances (1..8) advance in lock
@@ -585,8 +585,18 @@ class WaveRNN(nn.Module):
         softmax head, whose class labels are those of generate() on the same draws bit for bit.
         `noise` is then [steps][n_streams][512] Exp(1) draws by absolute step, the layout
         generate(noise=) takes; `mu_law` (default True, as generate_many) expands the emitted samples
-        as generate(mu_law=) does and is ignored for MoL models."""
-        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset, wide, mu_law)
+        as generate(mu_law=) does and is ignored for MoL models.
+
+        `rows=True` runs the session on the multi-row kernel (loop path 2; 9 when the weights are
+        streamed from HBM), the kernel generate() falls to for every model the XCD-resident ones do
+        not cover: MoL or RAW, any rnn / fc dims that are multiples of 4, any bit depth.  It is
+        opt-in: without it stream() accepts and refuses what it always did.  `n_streams` goes up to
+        one row block of the kernel for this model (ValueError beyond it, with the limit); `noise`
+        is [steps][n_streams][11] for MoL and [steps][n_streams][n_classes] Exp(1) draws for RAW;
+        `mu_law` as for wide RAW sessions.  With the same draws the session's samples are those of
+        generate() on the multi-row kernel (WRNN_PATH=rows).  A rows session advances alone
+        (push_streams refuses it), and `rows=True, wide=True` is a ValueError."""
+        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset, wide, mu_law, rows)
 
     def push_streams(self, pushes) -> list:
         """Advance several sessions of this model in one call: `pushes` is a sequence of
@@ -615,12 +625,13 @@ class WaveRNN(nn.Module):
         return [w.cpu().numpy() for w in members[0][0].loop.push_streams(members)]
 
     def generate_stream(self, mels, chunk_frames: int = 8, *, noise=None, seed: Optional[int] = None,
-                        row_offset: int = 0, wide: bool = False, mu_law: bool = True):
+                        row_offset: int = 0, wide: bool = False, mu_law: bool = True, rows: bool = False):
         """generate(mels, None, False, ...) as a generator of float64 chunks, for a mel known up
         front: mels [1][feat][T] (or [U][feat][T], chunks [U][m]) pushed `chunk_frames` at a time
         (or by the frame counts of a sequence).  The chunks concatenate to generate()'s output.
         `wide` is passed to stream(): up to 128 utterances in lock step on the many-row kernel.
-        `mu_law` likewise: a RAW model streams wide only, its samples mu-law expanded by default."""
+        `mu_law` likewise: a RAW model streams wide only, its samples mu-law expanded by default.
+        `rows` is passed to stream() too: the multi-row kernel's sessions, for any model."""
         device = next(self.parameters()).device
         mels = torch.as_tensor(mels, device=device).to(torch.float32)
         if mels.dim() != 3:
@@ -629,7 +640,7 @@ class WaveRNN(nn.Module):
         counts = [chunk_frames] * (-(-T // chunk_frames)) if isinstance(chunk_frames, int) else list(chunk_frames)
         if any(c < 1 for c in counts):
             raise ValueError("chunk_frames must be positive")
-        with self.stream(U, T, noise=noise, seed=seed, row_offset=row_offset, wide=wide, mu_law=mu_law) as s:
+        with self.stream(U, T, noise=noise, seed=seed, row_offset=row_offset, wide=wide, mu_law=mu_law, rows=rows) as s:
             f = 0
             for c in counts:
                 if f >= T:
@@ -741,7 +752,9 @@ class WaveRNNStream:
     WaveRNN.push_streams advances several sessions in one call, each at its own pace."""
 
     def __init__(self, model: WaveRNN, n_streams: int, total_frames: Optional[int], noise, seed: Optional[int],
-                 row_offset: int, wide: bool = False, mu_law: bool = True):
+                 row_offset: int, wide: bool = False, mu_law: bool = True, rows: bool = False):
+        if rows and wide:
+            raise ValueError("rows=True and wide=True name two kernels: a session runs on one")
         if wide and not 1 <= int(n_streams) <= 128:
             raise ValueError(f"a wide session has 1..128 utterances, not {n_streams!r}")
         device = next(model.parameters()).device
@@ -757,8 +770,10 @@ class WaveRNNStream:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         cfg, packed = model._melresnet_packed()
         self._session = FatchordStream(model.loop_handle(), model._upsample_spec(), cfg, packed, n_streams,
-                                       total_frames, nz, seed, row_offset, wide=wide, mu_law=bool(mu_law))
+                                       total_frames, nz, seed, row_offset, wide=wide, mu_law=bool(mu_law),
+                                       rows=bool(rows))
         self.wide = bool(wide)
+        self.rows = bool(rows)
         self.n_streams = n_streams
         self.lookahead_frames = self._session.lookahead_frames
 

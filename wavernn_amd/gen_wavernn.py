@@ -76,7 +76,12 @@ def main(argv=None):
             ap.error("--stream-chunk needs a positive frame count")
         from . import dsp
         model.eval()
-        chunks = list(model.generate_stream(mel, args.stream_chunk, seed=args.seed))
+        seed = args.seed if args.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        try:
+            chunks = list(model.generate_stream(mel, args.stream_chunk, seed=seed))
+        except NotImplementedError:
+            # no XCD-resident session kernel for this model: the multi-row kernel's sessions take any
+            chunks = list(model.generate_stream(mel, args.stream_chunk, seed=seed, rows=True, mu_law=hp.mu_law))
         dsp.save_wav(np.concatenate(chunks), out, hp.sample_rate)
     else:
         model.generate(mel, out, batched, target, overlap, hp.mu_law, seed=args.seed)

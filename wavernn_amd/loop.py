@@ -498,6 +498,8 @@ class FatchordLoop:
             members.append((s, mel, s._frames_of(mel), bool(final)))
         if not members:
             raise ValueError("push_streams needs at least one member")
+        if any(getattr(s, "rows", False) for s, _, _, _ in members):
+            raise ValueError("a rows session advances alone: its kernel steps all rows in lock step")
         if any(s.wide != members[0][0].wide for s, _, _, _ in members):
             raise ValueError("a group holds wide sessions or narrow ones, not both: they run different loop kernels")
         rows = sum(s.n_streams for s, _, _, _ in members)
@@ -716,13 +718,22 @@ class FatchordStream:
     [steps][n_streams][512] Exp(1) draws by absolute step (generate()'s layout), the class labels
     are those of generate() on the same draws bit for bit, and `mu_law=True` expands the emitted
     samples (C-ABI wrnn_stream_mu_law; ignored on a MoL loop; set_mu_law() changes it before the
-    first push)."""
+    first push).
+
+    `rows=True` opens the session on the multi-row kernel (C-ABI wrnn_stream_open_rows, last_path 2,
+    or 9 with streamed weights): any MoL or RAW loop the kernel runs, whatever its rnn / fc dims and
+    class count, `n_streams` up to one row block of it (the library states the limit).  `noise` is
+    [steps][n_streams][loop.noise_k] by absolute step; `mu_law` as for wide RAW sessions.  A rows
+    session advances alone: push_streams refuses it."""
 
     def __init__(self, loop: FatchordLoop, spec, mr_cfg, mr_packed: torch.Tensor, n_streams: int = 1,
                  total_frames: Optional[int] = None, noise: Optional[torch.Tensor] = None, seed: int = 0,
-                 row_offset: int = 0, wide: bool = False, mu_law: bool = False):
+                 row_offset: int = 0, wide: bool = False, mu_law: bool = False, rows: bool = False):
         self._s = None
         self.wide = bool(wide)
+        self.rows = bool(rows)
+        if self.rows and self.wide:
+            raise ValueError("rows=True and wide=True name two kernels: a session runs on one")
         if self.wide and not 1 <= int(n_streams) <= WIDE_ROWS:
             raise ValueError(f"a wide session has 1..{WIDE_ROWS} utterances, not {n_streams!r}")
         if getattr(loop, "_padded", False):
@@ -740,7 +751,8 @@ class FatchordStream:
         self.lookahead_frames = stream_lookahead(spec)
         s = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            opener = nat.lib().wrnn_stream_open_wide if self.wide else nat.lib().wrnn_stream_open
+            opener = nat.lib().wrnn_stream_open_rows if self.rows else \
+                nat.lib().wrnn_stream_open_wide if self.wide else nat.lib().wrnn_stream_open
             rc = opener(loop._h, ctypes.byref(spec.cfg), ctypes.byref(mr_cfg), mr_packed.data_ptr(),
                                             n_streams, -1 if total_frames is None else int(total_frames),
                                             noise.data_ptr() if noise is not None else None,
