@@ -334,6 +334,10 @@ int generate_xcd_rows(wrnn_t *h, const float *cond, const FrameSrc *fs, int B, i
                       uint64_t seed, int64_t row_offset, float *out, hipStream_t st, int n_terms, int state_w,
                       const Slab &slab, hipError_t (*launch)(const Args &, hipStream_t)) {
     const int N = kXcdWgs * n_terms;
+    constexpr bool kPanels = std::is_same_v<Args, XcdArgs>;   // the terms GEMM in whole panels (below)
+    // 8192 row-steps (168 MB of terms): 20 000 steps of 8 rows take 3.155 µs/step with the GEMM, as with one
+    // GEMM of all columns; panels of 512 or 2048 take 3.25 (rocBLAS's kernels for those shapes)
+    constexpr int kTermsPanel = 8192;
     if (int rc = blas_on(h, st)) return rc;
     if (fs) {   // frame-rate terms: W·(frames) once, then per chunk the nJ-tap sum (frame_terms.hip)
         const float one = 1.0f, zero = 0.0f;
@@ -358,8 +362,14 @@ int generate_xcd_rows(wrnn_t *h, const float *cond, const FrameSrc *fs, int B, i
     for (int b0 = 0; b0 < B; b0 += kXcds) {
         const int nb = std::min(kXcds, B - b0);
         const int Lc_max = (int)std::max(1.0, std::min((double)L, budget / ((double)nb * (N + h->KXc)) - 1.0));
-        if (grow(h, h->d_X, h->X_cap, (size_t)(Lc_max + 1) * nb * h->KXc) ||
-            grow(h, h->d_T, h->T_cap, (size_t)(Lc_max + 1) * nb * N) ||
+        // dense kernel: the terms GEMM runs in panels of kTermsPanel row-steps, the last one whole too (the
+        // buffers end on a panel; what it reads past the packed records only reaches terms rows nobody
+        // loads) — rocBLAS picks its kernel by the column count, and a chunk of 96 row-steps did not sum
+        // like the 776 of the same call in one launch: with one shape for every call, a row-step's terms
+        // are the same bits however the call is cut into launches
+        const size_t cols_max = (size_t)(Lc_max + 1) * nb;
+        const size_t cols_cap = kPanels ? (cols_max + kTermsPanel - 1) / kTermsPanel * kTermsPanel : cols_max;
+        if (grow(h, h->d_X, h->X_cap, cols_cap * h->KXc) || grow(h, h->d_T, h->T_cap, cols_cap * N) ||
             grow(h, h->d_xstate, h->xstate_cap, (size_t)nb * kXcdWgs * state_w))
             return WRNN_EHIP;
         if (dbg_steps > 0 && !dbg.p) {
@@ -376,10 +386,17 @@ int generate_xcd_rows(wrnn_t *h, const float *cond, const FrameSrc *fs, int B, i
                                                fs->hop, fs->nJ, fs->nf, fs->stride, fs->rb + b0, nb, t0, rows, st));
             } else {
                 HIP_TRY(h, launch_pack_cond_input(cond, h->CD, B, b0, nb, t0, rows, h->KXc, h->d_X, st));
-                if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, rows * nb, h->KXc,
-                                  &one, h->d_xWt, h->KXc, h->d_X, h->KXc, &zero, h->d_T, N) != rocblas_status_success)
-                    return fail(h, WRNN_EHIP, "rocblas_sgemm (conditioning terms) failed");
+                const int cols = rows * nb, step = kPanels ? kTermsPanel : cols;
+                for (int c0 = 0; c0 < cols; c0 += step)
+                    if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, step, h->KXc,
+                                      &one, h->d_xWt, h->KXc, h->d_X + (size_t)c0 * h->KXc, h->KXc, &zero,
+                                      h->d_T + (size_t)c0 * N, N) != rocblas_status_success)
+                        return fail(h, WRNN_EHIP, "rocblas_sgemm (conditioning terms) failed");
             }
+            // the dense kernel's one-shot launches form no sampler draws: the terms the sampler adds, Philox
+            // or injected, go into the padding of the chunk's terms rows and reach the loop with them
+            if constexpr (std::is_same_v<Args, XcdArgs>)
+                HIP_TRY(h, launch_xcd_draws(h->d_T, noise, seed, row_offset + b0, nb, B, b0, t0, rows, st));
             HIP_TRY(h, hipMemsetAsync(h->d_members, 0, kXcds * sizeof(int), st));
             Args a{};
             a.slab = h->d_xslab;

@@ -41,7 +41,10 @@ constexpr int kXNoise = 16;         // 11 MoL sampler terms, padded
 // Conditioning terms of one step for one workgroup (columns of the terms GEMM), floats:
 //   [0,48) P1 = W_ih1·cI, [48,96) P2 = W_ih2·[cI; a2]   (index u·3 + gate, u = local unit)
 //   [96,112) cI of the own units, [112,128) V1 = W1[:, R:]·a3 + b1, [128,144) V2 = W2[:, F:]·a4 + b2
-enum XTerm { XT_P1 = 0, XT_P2 = 48, XT_CI = 96, XT_V1 = 112, XT_V2 = 128, kXTerms = 160 };
+//   [144,160) one-shot launches: the row-step's 11 sampler terms, padded (launch_xcd_draws writes them over
+//   the GEMM's zeros, the same 16 floats in every workgroup's record); otherwise unused
+enum XTerm { XT_P1 = 0, XT_P2 = 48, XT_CI = 96, XT_V1 = 112, XT_V2 = 128, XT_NZ = 144, kXTerms = 160 };
+static_assert(XT_NZ + kXNoise == kXTerms, "the sampler record fills the terms record's padding");
 
 // Hand-off vectors of one XCD (granules {tag = step + 1, value}, plain stores that stay in the
 // XCD's L2, sc1 polls).  S (the GRU1 terms) is double-buffered by step parity.
@@ -171,6 +174,13 @@ static_assert(xcd_lds_layout().total * 4 <= 160 * 1024, "the XCD kernel's LDS im
 
 // host launchers (fatchord_xcd.hip)
 hipError_t launch_xcd(const XcdArgs &a, hipStream_t st);
+// The sampler terms of a one-shot launch's rows [0, nb) for the n terms rows of steps [t0, t0 + n), into
+// slot XT_NZ of every workgroup's record of `terms` (row dt·nb + k): the 11 terms the sampler adds to the
+// logits (mol_noise_term of the Philox draw keyed (seed, row0 + k, t0 + dt, kk), or of
+// noise[((t0 + dt)·Bt + b0 + k)·11 + kk] when draws are injected), zero-padded — formed once per row-step
+// instead of in the step loop of every workgroup.  After the terms GEMM / interpolation of the chunk.
+hipError_t launch_xcd_draws(float *terms, const float *noise, unsigned long long seed, long long row0, int nb, int Bt,
+                            int b0, int t0, int n, hipStream_t st);
 hipError_t launch_xcd_group(const XcdGroupArgs &g, hipStream_t st);
 hipError_t launch_xcd_list(const XcdListArgs &g, hipStream_t st);
 hipError_t prepare_xcd_kernel(int max_lds_bytes);

@@ -28,7 +28,8 @@
 // t+1 → publish (hop S, double-buffered); h2 published by the GRU2 waves after "y gathered",
 // gathered by wave 6 → W_hh2·h2 (VGPR rows of waves 1..7 + LDS rows) for the next GRU2; S
 // gathered by waves 1, 2, 5 and fc2 wave 4, a quarter each; the conditioning terms and noise of
-// step t+2 into the LDS ring (wave 7).
+// step t+2 into the LDS ring (wave 7; one-shot launches find the sampler's noise terms prepared in the
+// terms record, the windowed ones form them there).
 //
 // Membership: each workgroup reads its XCC id from the hardware register and takes an index
 // from a per-XCD arrival counter, so correctness never depends on the dispatcher's placement
@@ -69,6 +70,12 @@ namespace wrnn {
 #ifndef WRNN_XCD_SQ3_WAVE
 #define WRNN_XCD_SQ3_WAVE 4
 #endif
+// 1: the sampler wave's first F2 poll waits for fc2 wave 4's LDS hand-off (hop F2 cannot be complete before
+// the workgroup's own line is on its way): from its GRU1-term publish on, wave 0 polled F2 for 0.9 µs with 8
+// loads a round, on the SIMD of fc2 wave 4 and through the L2 that carries hops F1 and F2; 0: as before (A/B)
+#ifndef WRNN_XCD_F2_GATE
+#define WRNN_XCD_F2_GATE 1
+#endif
 #ifndef WRNN_XCD_STAMP_W13
 #define WRNN_XCD_STAMP_W13 5    // stamped builds: the wave whose W_hh2·h2 end is stamp 13 (6: the h2 gatherer)
 #endif
@@ -100,7 +107,8 @@ namespace wrnn {
             for (int t = t0; t < t0 + 3; ++t) {                                                               \
                 if (t <= t_terms)                                                                             \
                     for (int i = tid; i < kXTerms; i += kXThreads) RING(t)[i] = TERMS(t)[i];                  \
-                if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);                        \
+                if constexpr (kWin)                                                                           \
+                    if (wave == 1 && lane < 11 && t < nz_hor) NZ(t)[lane] = noise_term(t);                    \
             }                                                                                                 \
         }                                                                                                     \
         resume = t0 > 0;                                                                                      \
@@ -324,8 +332,12 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
     // of an engine publishes the terms of its row gh0 + 2·li + e
     const bool gh1w = wave == 0 || wave == 3 || wave == 4 || wave == 5 || wave == 7;
     const int gh0 = wave == 0 ? 0 : wave == 7 ? 40 : 10 * (wave - 2);
-    // sampler noise of step t → NZ(t): u1 → log(-log u1) (distribution.py:107), u2 → log u2 − log(1 − u2) (:119)
-    auto noise_term = [&](int t) -> float {
+    // sampler noise of step t → NZ(t): u1 → log(-log u1) (distribution.py:107), u2 → log u2 − log(1 − u2) (:119).
+    // One-shot launches (!kWin) find these terms in slot XT_NZ of the step's terms record, written per
+    // row-step by xcd_draws_kernel ahead of the launch, so they come into the ring with the record: a Philox
+    // word and three logf per step, the same in all 32 workgroups, stood on wave 7's way to the step-end
+    // barrier.  The windowed, grouped and list launches still form them here.
+    [[maybe_unused]] auto noise_term = [&](int t) -> float {
         float uu;
         if constexpr (kGrp) {
             if (rw.noise) uu = rw.noise[(size_t)t * (size_t)rw.noise_ld + lane];
@@ -534,9 +546,14 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
             // lane l: logits (2jp, 2jp+1), jp = l & 15, of producers 8·(l >> 4) + m, m = 0..7:
             // one 16-byte load each (256 B apart: immediates)
             const int jp = lane & 15, pg = lane >> 4;
-            const float ua = NZ(t)[jp < 5 ? 2 * jp : 0], ub = NZ(t)[jp < 5 ? 2 * jp + 1 : 0], u10 = NZ(t)[10];
+            const float *nzt = kWin ? NZ(t) : tr + XT_NZ;
+            const float ua = nzt[jp < 5 ? 2 * jp : 0], ub = nzt[jp < 5 ? 2 * jp + 1 : 0], u10 = nzt[10];
             const float b3a = cst[XC_B3 + 2 * jp], b3b = cst[XC_B3 + 2 * jp + 1];
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // no F2 poll round before fc2 wave 4 has handed its partials to wave 3 (the tag word of its first
+            // pair; wave 4 stores on every path): ≈ 0.05 µs before wave 3's publish, ≈ 0.4 µs before the hop
+            // can complete, so the poller is in flight when the lines land
+            if (WRNN_XCD_F2_GATE) wait_flag(reinterpret_cast<int *>(f2x) + 1, tag);
             const __amdgpu_buffer_rsrc_t rf = hop_rsrc(XG(XH_F2));
             const int goff = pg * 8 * kXF2Line * 8 + jp * 16;
             const unsigned long long c0 = __builtin_amdgcn_s_memrealtime();
@@ -700,7 +717,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
                     if (t + 2 >= t0 + 3) {
                         if (t + 2 <= t_terms && lane < kXTerms / 4)
                             reinterpret_cast<f4v *>(RING(t + 2))[lane] = reinterpret_cast<const f4v *>(TERMS(t + 2))[lane];
-                        if (t + 2 < nz_hor && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
+                        if constexpr (kWin)
+                            if (t + 2 < nz_hor && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
                     }
                 }
                 goto step_end;
@@ -738,7 +756,8 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
                 // issued here and stored after the wave's W_hh2 pass: 3.25 -> 3.30 us/step)
                 if (t + 2 <= t_terms && lane < kXTerms / 4)
                     reinterpret_cast<f4v *>(RING(t + 2))[lane] = reinterpret_cast<const f4v *>(TERMS(t + 2))[lane];
-                if (t + 2 < nz_hor && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
+                if constexpr (kWin)
+                    if (t + 2 < nz_hor && lane < 11) NZ(t + 2)[lane] = noise_term(t + 2);
                 XSTAMPW(12, 7);
             }
             wait_flag(h2ready, tag);
@@ -795,6 +814,32 @@ __global__ __launch_bounds__(kXThreads, 2) void fatchord_xcd_kernel(
 #define WRNN_K_XCD_WIN fatchord_xcd_kernel<false, true>   // streaming sessions (no stamps)
 #define WRNN_K_XCD_GRP fatchord_xcd_kernel<false, true, true>   // group pushes: a window per row
 #define WRNN_K_XCD_LST fatchord_xcd_kernel<false, true, true, true>   // list launches: a queue of pieces per XCD
+
+// The sampler terms of a one-shot launch (fatchord_xcd.h: launch_xcd_draws): one thread per float of a
+// row-step's record, stored to slot XT_NZ of all kXcdWgs workgroup records of that terms row.
+// noise_term's two device functions in this file, under this file's flags: the bits the loop formed.
+__global__ void xcd_draws_kernel(float *terms, const float *noise, unsigned long long seed, long long row0, int nb, int Bt,
+                                 int b0, int t0, int n) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)n * nb * kXNoise) return;
+    const int kk = (int)(i % kXNoise), lr = (int)((i / kXNoise) % nb), t = t0 + (int)(i / ((long long)kXNoise * nb));
+    float v = 0.0f;
+    if (kk < 11) {
+        const float uu = noise ? noise[((size_t)t * Bt + b0 + lr) * 11 + kk]
+                               : philox_noise(seed, (unsigned long long)(row0 + lr), (uint32_t)t, (uint32_t)kk, 1);
+        v = mol_noise_term(uu, kk);
+    }
+    float *rec = terms + (size_t)(i / kXNoise) * (kXcdWgs * kXTerms) + XT_NZ + kk;
+    for (int c = 0; c < kXcdWgs; ++c) rec[(size_t)c * kXTerms] = v;
+}
+
+hipError_t launch_xcd_draws(float *terms, const float *noise, unsigned long long seed, long long row0, int nb, int Bt,
+                            int b0, int t0, int n, hipStream_t st) {
+    const long long m = (long long)n * nb * kXNoise;
+    hipLaunchKernelGGL(xcd_draws_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, terms, noise, seed, row0,
+                       nb, Bt, b0, t0, n);
+    return hipGetLastError();
+}
 
 hipError_t launch_xcd(const XcdArgs &a, hipStream_t st) {
     XcdArgs args = a;
