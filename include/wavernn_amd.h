@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define WRNN_ABI_VERSION 6
+#define WRNN_ABI_VERSION 7
 
 enum wrnn_status {
     WRNN_OK = 0,
@@ -99,6 +99,12 @@ typedef struct {
                                 4 rows per XCD), 32. */
     int32_t xcdm_rows;       /* XCD-resident many-row kernel (MoL rnn/fc 512): rows per launch
                                 (0: unavailable)                                           (ABI 5) */
+    /* What the last multi-row call chose (ABI 7): wrnn_generate on the multi-row or the deepmind rows
+       kernel (last_path 2, 9, 3, 10) or a rows session's push.  All 0 after any other call. */
+    int32_t last_row_groups; /* 1, or 2: the rows of a block in two groups on half the workgroups each */
+    int32_t last_row_blocks; /* row blocks (launch loops of <= 256 rows) the call ran                */
+    int32_t last_block_rows; /* rows of its first block, after any shrink to what LDS holds          */
+    int32_t last_tile_rows;  /* rows per register tile (TB) of its first block                       */
 } wrnn_info;
 
 /* Create a handle on `device` (replaces WaveRNN.__init__ for the loop's dims,

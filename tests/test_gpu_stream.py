@@ -133,6 +133,39 @@ def test_dims_not_multiple_of_4_dropin_generate():
     mel = torch.from_numpy(syn.make_mel(d.feat_dims, 40, 761))[None]
     out = m.generate(mel, None, False, 11000, 550, False, seed=3, verbose=False)
     assert out.shape[0] == (40 - 1) * d.hop_length and np.isfinite(out).all() and np.abs(out).max() <= 1.0
+    _dropin_vs_oracle(d, m, mel)
+
+
+def _dropin_vs_oracle(d, m, mel):
+    """generate() on injected draws against oracle.generate on the original (unpadded) dims: MoL within
+    2·MOL_TOL (the bound of test_gpu_regimes.py::test_dropin_generate_hot_regime for this entry), RAW
+    at rtol 1e-12 (test_gpu_parity.py::test_generate_dropin_vs_reference)."""
+    from oracle import oracle
+    T = mel.shape[-1]
+    state = syn.make_fatchord_state(d, 760)
+    noise = syn.make_noise(d.mode, 1, T * d.hop_length, d.n_classes, 762)
+    ref = oracle.generate(state, d, mel[0].numpy(), False, 11000, 550, False, noise)
+    got = m.generate(mel, None, False, 11000, 550, False, noise=noise, verbose=False)
+    assert got.dtype == np.float64 and got.shape == ref.shape == ((T - 1) * d.hop_length,)
+    if d.mode == "RAW":
+        np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-300)
+    else:
+        diff = np.abs(got - ref)
+        first = int(np.argmax(diff > 1e-6)) if (diff > 1e-6).any() else None
+        assert diff.max() <= 2 * gf.MOL_TOL, f"max |Δ| {diff.max():.3g}, first sample over 1e-6: {first}"
+
+
+def test_dims_not_multiple_of_4_dropin_generate_raw():
+    """The RAW variant (bits 6) of the odd dims through the drop-in generate()."""
+    from wavernn_amd.fatchord_version import WaveRNN
+    d = syn.FatchordDims(rnn_dims=30, fc_dims=37, bits=6, compute_dims=16, res_out_dims=20, res_blocks=1,
+                         mode="RAW")
+    m = WaveRNN(**d.ctor_kwargs()).to(DEV)
+    m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(d, 760).items()})
+    mel = torch.from_numpy(syn.make_mel(d.feat_dims, 40, 761))[None]
+    out = m.generate(mel, None, False, 11000, 550, False, seed=3, verbose=False)
+    assert out.shape[0] == (40 - 1) * d.hop_length and np.isfinite(out).all() and np.abs(out).max() <= 1.0
+    _dropin_vs_oracle(d, m, mel)
 
 
 @pytest.mark.parametrize("bits,B", [(10, 1), (10, 3), (11, 2)])

@@ -161,7 +161,7 @@ def test_entry_points_are_declared_exported_and_bound():
         m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
         assert m, name
         assert len(m.group(1).split(",")) == nargs == len(getattr(lib, name).argtypes)
-    assert "#define WRNN_ABI_VERSION 6" in hdr and nat.ABI_VERSION == 6      # additive: the version stays
+    assert "#define WRNN_ABI_VERSION 7" in hdr and nat.ABI_VERSION == 7      # additive: the version stays (7: wrnn_info grew)
     fields = re.search(r"typedef struct \{([^{}]*)\}\s*wrnn_post_fold_entry;", hdr).group(1)
     assert [f.split()[-1] for f in fields.replace(",", ";").split(";") if f.strip()] == ["*y", "dst", "rows", "wave_len"]
     assert condition.POST_FOLD_ENTRY.itemsize == 24 and condition.POST_FOLD_ENTRY.names == ("y", "dst", "rows", "wave_len")

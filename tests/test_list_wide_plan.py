@@ -183,4 +183,4 @@ def test_entry_points_are_declared_exported_and_bound():
         m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
         assert m, name
         assert len(m.group(1).split(",")) == nargs == len(getattr(lib, name).argtypes)
-    assert "#define WRNN_ABI_VERSION 6" in hdr      # additive: the version stays
+    assert "#define WRNN_ABI_VERSION 7" in hdr      # additive: the version stays (7: wrnn_info grew)

@@ -1140,7 +1140,11 @@ int wrnn_create(const wrnn_config *cfg, int device, wrnn_t **out) {
     set_group_partition(*h);
     if (h->g2.ok) {
         PartScope ps(*h, h->g2, true);
-        HIP_TRY(h, rows_occupancy(&per_cu, rows_lds_bytes(*h, 1, 1)));
+        // the partition is accepted on its fit with the MoL head left in HBM (set_group_partition); where
+        // the head does not fit beside the body a launch leaves it there, so residency is asked for that
+        // size (with the head counted, occupancy was 0 and such a model silently kept one group)
+        const bool head = rows_tile_for(*h, 1) > 0;
+        HIP_TRY(h, rows_occupancy(&per_cu, rows_lds_bytes(*h, 1, 1, head)));
         if (per_cu * h->num_cus < 2 * h->rG) h->rows_ok = false;
     }
     // one MoL row: the role-split kernel (compile-time dims) when its grid and LDS fit; an
@@ -1413,6 +1417,10 @@ int wrnn_query(const wrnn_t *h, wrnn_info *info) {
         info->rows_units_rnn = h->dmU;
         info->last_path = h->last_path;
         info->xcd_rows = h->dx_ok ? kDxRowsMax : 0;
+        info->last_row_groups = h->last_row_groups;
+        info->last_row_blocks = h->last_row_blocks;
+        info->last_block_rows = h->last_block_rows;
+        info->last_tile_rows = h->last_tile_rows;
         return WRNN_OK;
     }
     const bool rows_only = h->max_rows < 1;      // e.g. rnn 896 with block-sparse GRU weights
@@ -1431,6 +1439,10 @@ int wrnn_query(const wrnn_t *h, wrnn_info *info) {
     info->last_path = h->last_path;
     info->xcd_rows = (h->xcd_ok || h->xcds_ok) ? kXcds : 0;
     info->xcdm_rows = h->xcdm_ok ? kXcds * 4 * h->xcdm_nq : 0;
+    info->last_row_groups = h->last_row_groups;
+    info->last_row_blocks = h->last_row_blocks;
+    info->last_block_rows = h->last_block_rows;
+    info->last_tile_rows = h->last_tile_rows;
     return WRNN_OK;
 }
 

@@ -209,7 +209,7 @@ int wrnn_generate_list(wrnn_t *h, const wrnn_upsample_cfg *ucfg, const float *co
     HIP_TRY(h, hipMemsetAsync(h->d_lxg, 0, (size_t)U * kXXcdStride * 8, st));   // tags restart at 1 in every utterance
     HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
     HIP_TRY(h, hipEventRecord(h->ev0, st));
-    h->last_path = (int)path;
+    set_last_path(h, (int)path);
     const float one = 1.0f, zero = 0.0f;
     const int rc = list_frame_terms(h, mel, aux, T, U, hop, nJ, jlo, arena, N, 0, st, [&](const float *X, int m, float *Cm) -> int {
         if (rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, N, m, h->KXc, &one, h->d_xWt,

@@ -68,6 +68,7 @@ int generate_rows(wrnn_t *h, const float *cond, int B, int L, const float *noise
     for (int b0 = 0; b0 < B;) {
         RowsBlock k;
         if (int rc = rows_block(h, grouped, B - b0, L, &k)) return rc;
+        note_row_block(h, k.ng, k.Bl, k.TB);
         if (grow(h, h->d_X, h->X_cap, (size_t)k.Lc_max * k.Bg * k.KXg) || grow(h, h->d_T, h->T_cap, k.ng * k.T_grp) ||
             grow(h, h->d_act, h->act_cap, k.ng * k.act_grp) || grow(h, h->d_state, h->state_cap, k.ng * k.state_grp))
             return WRNN_EHIP;
@@ -178,9 +179,12 @@ int generate_dm(wrnn_t *h, int B, int L, const float *noise, uint64_t seed, int6
         int Bl = std::min(B - b0, kRowsMax);
         auto group_rows = [&](int bl, int g) { const int b_0 = (bl + ng - 1) / ng; return g == 0 ? b_0 : bl - b_0; };
         while (Bl > 1 && dm_tile_for(*h, group_rows(Bl, 0)) == 0) --Bl;
+        // two groups: never leave one row for the next block (rows_block: 257 rows are 255 + 2)
+        if (ng == 2 && B - b0 - Bl == 1 && Bl > 2) --Bl;
         const int Bg = group_rows(Bl, 0);
         const int TB = dm_tile_for(*h, Bg);
         if (TB == 0) return fail(h, WRNN_EUNSUPPORTED, "DM: one row of state does not fit LDS");
+        note_row_block(h, ng, Bl, TB);
         const int SW = dm_state_width(h->dmU);
         const size_t act_grp = (size_t)kDmHops * 2 * Bg * h->KA, state_grp = (size_t)h->G * Bg * SW + 2 * Bg;
         if (grow(h, h->d_act, h->act_cap, ng * act_grp) || grow(h, h->d_state, h->state_cap, ng * state_grp))
@@ -655,6 +659,9 @@ int rows_block(wrnn_t *h, bool grouped, int rows_left, int steps, RowsBlock *out
     int Bl = std::min(rows_left, kRowsMax);
     auto group_rows = [&](int bl, int g) { const int b_0 = (bl + ng - 1) / ng; return g == 0 ? b_0 : bl - b_0; };
     while (Bl > 1 && rows_tile_for(*h, group_rows(Bl, 0)) == 0 && rows_tile_for(*h, group_rows(Bl, 0), false) == 0) --Bl;
+    // two groups: never leave one row for the next block (its second group would have no rows: a launch of
+    // no blocks for its terms and G/2 workgroups looping over nothing), 257 rows are 255 + 2
+    if (ng == 2 && rows_left - Bl == 1 && Bl > 2) --Bl;
     const int Bg = group_rows(Bl, 0);          // rows of group 0 (>= those of group 1)
     k.Bl = Bl;
     k.Bg = Bg;
@@ -902,7 +909,7 @@ static int run_loop(wrnn_t *h, LoopPath path, const float *cond, const FrameSrc 
              uint64_t seed, int64_t row_offset, float *out, int32_t *labels, hipStream_t st) {
     HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
     HIP_TRY(h, hipEventRecord(h->ev0, st));
-    h->last_path = path == P_ROWS && h->rows_gw ? 9 : path == P_DM && h->dm_gw ? 10 : (int)path;
+    set_last_path(h, path == P_ROWS && h->rows_gw ? 9 : path == P_DM && h->dm_gw ? 10 : (int)path);
     int rc = WRNN_OK;
     switch (path) {
         case P_DX: rc = generate_dx(h, B, L, noise, seed, row_offset, out, labels, st); break;

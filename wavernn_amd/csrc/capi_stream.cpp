@@ -677,7 +677,8 @@ static int rows_launches(wrnn_stream *s, const StreamPush &p, hipStream_t st) {
     // the handle's hop areas carry step tags: whatever a one-shot call or another session left there
     // since the last push must not satisfy a poll of this one
     if (int rc = rows_reset(h, k, true, st)) return rc;
-    h->last_path = h->rows_gw ? 9 : (int)P_ROWS;
+    set_last_path(h, h->rows_gw ? 9 : (int)P_ROWS);
+    note_row_block(h, k.ng, k.Bl, k.TB);
     RowsRun r{};
     r.cond = s->d_cond;
     r.cond_t0 = p.S_old;
@@ -786,7 +787,7 @@ int wrnn::host::wide_run_launches(wrnn_t *h, const std::vector<WideLaunch> &ls, 
     // ---- queuing begins
     HIP_TRY(h, h->wtab.upload(ntab + (folds ? fold_tab_records(ntab) : 0), st));
     HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
-    h->last_path = (int)P_XCDM;
+    set_last_path(h, (int)P_XCDM);
     // wrnn_elapsed_ms: the loop share of this push (interpolation, draws, resets and persistent
     // launches of all its rounds), so a caller can split a tick into conditioning and loop
     HIP_TRY(h, hipEventRecord(h->ev0, st));
@@ -901,7 +902,7 @@ int wrnn_stream_push(wrnn_stream_t *s, const float *mel, int n, int final, doubl
     }
     if (p.S_new > p.S_old) {
         HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
-        h->last_path = (int)s->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
+        set_last_path(h, (int)s->path);  // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
         int rc;
         if (s->rows) rc = rows_launches(s, p, st);
         else if (s->wide) rc = wide_group_launches(h, &s, &p, 1, st);
@@ -935,7 +936,7 @@ static int group_launches(wrnn_t *h, wrnn_stream *const *ss, const StreamPush *p
             HIP_TRY(h, ensure(ss[i]->d_T, ss[i]->T_cap, (size_t)(steps + 1) * ss[i]->U * N));
         }
     HIP_TRY(h, hipMemsetAsync(h->d_ctl, 0, kCtlWords * sizeof(int), st));
-    h->last_path = (int)ss[0]->path;   // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
+    set_last_path(h, (int)ss[0]->path);  // the timing events stay the last wrnn_generate's (wrnn_elapsed_ms)
     for (int off = 0; off < longest; off += Lc_max) {
         GroupArgs g{};
         g.a.slab = h->d_xslab;

@@ -144,6 +144,9 @@ struct wrnn_ctx {
     RowsPart g2{};
     rocblas_handle blas = nullptr;
     int last_path = 0;                              // 1 = latency, 2 = rows, 3 = deepmind, 4 = split, 5 = xcd, 6 = xcd sparse
+    // what the last multi-row call (generate_rows, generate_dm, a rows session's push) chose: row groups,
+    // row blocks, rows and tile rows of its first block; zeros after any other call (set_last_path)
+    int last_row_groups = 0, last_row_blocks = 0, last_block_rows = 0, last_tile_rows = 0;
     // deepmind_version (WRNN_MODE_DM): deepmind_rows.hip
     wrnn::DmSlab ds{};
     int dmU = 0, dmUO = 0, dmUO2 = 0;
@@ -214,6 +217,20 @@ constexpr int kCtlWords = 8;
 inline int fail(wrnn_t *h, int code, const std::string &msg) {
     if (h) h->err = msg;
     return code;
+}
+
+// The kernel a call runs (wrnn_info.last_path); the multi-row runners fill the last_row_* fields after it
+inline void set_last_path(wrnn_t *h, int path) {
+    h->last_path = path;
+    h->last_row_groups = h->last_row_blocks = h->last_block_rows = h->last_tile_rows = 0;
+}
+// One row block of a multi-row call: the first one's choices are what wrnn_info reports
+inline void note_row_block(wrnn_t *h, int groups, int rows, int tile) {
+    if (h->last_row_blocks++ == 0) {
+        h->last_row_groups = groups;
+        h->last_block_rows = rows;
+        h->last_tile_rows = tile;
+    }
 }
 
 #define HIP_TRY(h, expr)                                                                      \
