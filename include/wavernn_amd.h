@@ -717,6 +717,76 @@ typedef struct {
 int wrnn_postprocess_list_folds(const wrnn_post_fold_entry *entries, int U, int steps, int overlap, int max_wave_len,
                                 int mu_law, int n_classes, int fade_len, double *wave, void *stream);
 
+/* ---- Mel front end: wav in, the normalised mel generate() takes out (additive, same ABI) --------
+ * The reference's melspectrogram (utils/dsp.py:41-81) on the device, one launch for any set of
+ * frames of any set of signals.  The reference calls librosa; this implements the published
+ * definitions, pinned to a float64 restatement of them (tests/melspec_ref.py), not to librosa's
+ * output:
+ *   yp = reflect-pad(y, n_fft/2) (edge excluded);  T = 1 + len(y)/hop_length frames, frame t =
+ *   yp[t·hop : t·hop + n_fft];  window = periodic Hann of win_length, zero-padded to n_fft with
+ *   l = (n_fft − win_length)/2 zeros on the left;  |rfft|;  Slaney mel filterbank (fmin .. sr/2,
+ *   area-normalised);  clip((20·log10(max(1e-5, S)) − min_level_db) / −min_level_db, 0, 1).
+ * Tables are built on the host in float64 and rounded once to float32; the kernel computes in
+ * float32, one workgroup per frame, so a frame's value does not depend on the other frames or
+ * signals of the launch: the same frame is bit-identical one-shot, chunked and streamed.
+ * Taps whose window value is zero (the zero padding, a Hann window's first sample) are never read.
+ *
+ * WRNN_EUNSUPPORTED (decided without a launch) unless n_fft is a power of two in 256..4096,
+ * 1 <= win_length <= n_fft, hop_length >= 1, num_mels <= 128 and 0 <= fmin < sample_rate/2;
+ * WRNN_EINVAL for a signal shorter than n_fft/2 + 1 samples (the reflect padding's own limit).
+ * Errors leave their text in wrnn_cond_last_error. */
+typedef struct {
+    int32_t sample_rate;     /* 22050 */
+    int32_t n_fft;           /* 2048 */
+    int32_t hop_length;      /* 275 */
+    int32_t win_length;      /* 1100 */
+    int32_t num_mels;        /* 80 */
+    float fmin;              /* 40 */
+    float min_level_db;      /* -100 */
+} wrnn_melspec_cfg;
+/* Frames of a signal of n_samples: 1 + n_samples / hop_length (negative: WRNN_E*). */
+int64_t wrnn_melspec_frames(const wrnn_melspec_cfg *cfg, int64_t n_samples);
+/* The tables (host functions, no GPU): wrnn_melspec_table_floats(cfg) floats, M = n_fft/2 —
+ *   [0, 8)            first weighted tap, weighted taps, filterbank weights, then zeros
+ *   win   [n_fft]     the zero-padded window
+ *   twM   [2·M]       (cos, −sin)(2πn/M), n < M      — the M-point complex FFT of the even/odd packing
+ *   twN   [2·(M + 1)] (cos, −sin)(2πk/n_fft), k <= M — its post-twiddle pass
+ *   start [num_mels], len [num_mels], off [num_mels]  per band: first non-zero bin, bins, offset in w
+ *   w     [Σ len]     the bands' non-zero weights
+ * The caller copies them to the device once and passes that pointer as `tables`. */
+int wrnn_melspec_table_floats(const wrnn_melspec_cfg *cfg);
+int wrnn_melspec_tables(const wrnn_melspec_cfg *cfg, float *host_out);
+/* U device signals wav[u] of n[u] samples → U device mels, mel[u][band·ld[u] + t] for t < T_u
+ * (ld[u] >= T_u: a caller may write straight into a padded tensor; the padding is not touched).
+ * The pointer and length arrays are host arrays.  `scratch` is a device buffer of at least
+ * WRNN_MELSPEC_SCRATCH_PER_SIGNAL·U bytes the call fills with its job list; it must stay untouched
+ * until the launch has run.  One launch, queued on `stream`.  The job list is copied from pageable
+ * host memory, which HIP completes on the host before the call returns: the call may therefore wait
+ * for earlier work on `stream` (a caller that pipelines should give the front end a stream of its
+ * own and order it with events); the kernel itself runs asynchronously.  The same holds for
+ * wrnn_melspec_window and wrnn_melspec_windows. */
+#define WRNN_MELSPEC_SCRATCH_PER_SIGNAL 64
+int wrnn_melspec(const wrnn_melspec_cfg *cfg, const float *tables, const float *const *wav, const int *n, int U,
+                 float *const *mel, const int *ld, void *scratch, void *stream);
+/* Frames t0 .. t0 + nt − 1 of a signal of which samples [s0, s0 + ns) are resident at wav_tail
+ * (device) → mel[band·ld + (t − t0)].  `total` is the signal's length, or −1 while it is not known:
+ * reflection applies at the left edge always and at the right edge only with a known total.
+ * WRNN_EINVAL (nothing queued) when a frame reads a sample that is not resident.
+ * wrnn_melspec_windows is the same for U signals in one launch (host arrays of U entries). */
+int wrnn_melspec_window(const wrnn_melspec_cfg *cfg, const float *tables, const float *wav_tail, int64_t s0, int ns,
+                        int64_t total, int t0, int nt, float *mel, int ld, void *scratch, void *stream);
+int wrnn_melspec_windows(const wrnn_melspec_cfg *cfg, const float *tables, const float *const *wav_tail, const int64_t *s0,
+                         const int *ns, const int64_t *total, const int *t0, const int *nt, int U, float *const *mel,
+                         const int *ld, void *scratch, void *stream);
+/* Streaming, pure host: with `received` samples in, frames 0 .. *frames_ready − 1 are final, and
+ * samples before *keep_from are needed by no later frame (whatever the signal's eventual length).
+ * With [wlo, whi) the weighted taps, frame t is final once received >= t·hop + whi − n_fft/2 (for
+ * the default geometry t·hop + 550) and frame 0's mirrored samples are in (received >= n_fft/2 − wlo
+ * + 1; the same 550 there).  final != 0: `received` is the whole signal, all 1 + received/hop frames
+ * are ready (WRNN_EINVAL below n_fft/2 + 1 samples). */
+int wrnn_melspec_plan(const wrnn_melspec_cfg *cfg, int64_t received, int final, int64_t *frames_ready,
+                      int64_t *keep_from);
+
 /* Message of the last failed stateless call on this thread. */
 const char *wrnn_cond_last_error(void);
 

@@ -43,6 +43,10 @@ carries 8 · 275 / 22 050 s of audio, so they are when the tick's wall time stay
 --raw adds leg (r) in the same invocation: leg (b) on the RAW 9-bit rnn / fc 512 model (reference
 geometry, Philox, mu-law on) — the many-row kernel's softmax head, which adds the f2 and logits hops
 to every step — and the ratio of its loop share to leg (b)'s of the same run.
+--audio adds leg (p) in the same invocation: leg (b) fed PCM instead of mel — every session pushes
+8 · 275 samples per tick, the tick stages every session's PCM tail, computes the frames that became
+final in ONE front-end launch (wrnn_melspec_windows) and hands them to the same wide group push —
+and the difference of its tick to leg (b)'s: the front end's cost per tick.
 
     python tools/stream_latency.py --rows rnn256 dense896 raw512 [--chunks 4 8 32] [--reps 3] [--frames 101]
                                    [--out profiles/stream_rows_latency.jsonl]
@@ -246,18 +250,68 @@ def _wide_ticks(model, mels, c, wide, dev):
     return np.concatenate([torch.cat(o, 1).cpu().numpy() for o in out], 0), ticks
 
 
-def wide_case(model, N, legs, reps, dev, d, raw_model=None):
+def _wide_audio_ticks(model, pcms, c, dev):
+    """Leg (p): N wide U = 1 sessions fed PCM (`pcms` [1][samples] each), c·hop samples per tick, then
+    the flush (the remaining frames, and the empty final push).  → what _wide_ticks returns, the
+    third entry of a tick being the host ms spent staging the PCM and queueing the front end."""
+    loop = model.loop_handle()
+    N, NS, hop = len(pcms), pcms[0].shape[1], model.hop_length
+    sess = [model.stream(1, total_samples=NS, seed=1000, row_offset=i, wide=True) for i in range(N)]
+    feeds = [s._audio_feed() for s in sess]
+    front = feeds[0].front
+    out, ticks = [[] for _ in range(N)], []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    try:
+        f = 0
+        while not sess[0]._session.finished:
+            n = min(c * hop, NS - f)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            e0.record()
+            staged = [fd.stage(p[:, f:f + n] if n else None, final=n == 0) for fd, p in zip(feeds, pcms)]
+            jobs = [j for _, js, _ in staged for j in js]
+            mels = front.windows(jobs) if jobs else []
+            t1 = time.perf_counter()
+            pushes = [(s._session, mels[i][None] if jobs else None, False) for i, s in enumerate(sess)]
+            got = loop.push_streams(pushes, check=False)
+            if n == 0:
+                got = [torch.cat([a, b], 1) for a, b in
+                       zip(got, loop.push_streams([(s._session, None, True) for s in sess], check=False))]
+            e1.record()
+            torch.cuda.synchronize(dev)
+            wall = (time.perf_counter() - t0) * 1e3
+            for fd, (state, _, _) in zip(feeds, staged):
+                fd.commit(state)
+            ticks.append((wall, e0.elapsed_time(e1), (t1 - t0) * 1e3, int(bool(jobs))))
+            for i, w in enumerate(got):
+                out[i].append(w)
+            f += n
+        loop.check()
+    finally:
+        for s in sess:
+            s.close()
+    return np.concatenate([torch.cat(o, 1).cpu().numpy() for o in out], 0), ticks
+
+
+def wide_case(model, N, legs, reps, dev, d, raw_model=None, pcm_leg=False):
     """--wide N (module docstring): one JSON line per leg (raw_model: leg r after the others)."""
     med = statistics.median
     T, c = 401, 8
     mels = [torch.from_numpy(syn.make_mel(d.feat_dims, T, seed=10 + i))[None].to(dev) for i in range(N)]
     audio_ms = c * d.hop_length / d.sample_rate * 1e3
     audio, loop_ms = {}, {}
-    for leg in list(legs) + (["r"] if raw_model is not None else []):
-        wide = leg in ("b", "r")
+    pcms = [torch.from_numpy(0.1 * np.random.default_rng(10 + i).standard_normal((1, (T - 1) * d.hop_length))
+                             .astype(np.float32)).to(dev) for i in range(N)] if pcm_leg else None
+    wall = {}
+    for leg in list(legs) + (["r"] if raw_model is not None else []) + (["p"] if pcm_leg else []):
+        wide = leg in ("b", "r", "p")
         mdl = raw_model if leg == "r" else model
-        _wide_ticks(mdl, mels, c, wide, dev)
-        runs = [_wide_ticks(mdl, mels, c, wide, dev) for _ in range(reps)]
+        if leg == "p":
+            _wide_audio_ticks(mdl, pcms, c, dev)
+            runs = [_wide_audio_ticks(mdl, pcms, c, dev) for _ in range(reps)]
+        else:
+            _wide_ticks(mdl, mels, c, wide, dev)
+            runs = [_wide_ticks(mdl, mels, c, wide, dev) for _ in range(reps)]
         audio[leg] = runs[0][0]
         full = [[t for t in r[1] if t[3]][1:-1] for r in runs]   # ticks of 8 frames with a launch; not the first, not the flush
 
@@ -267,13 +321,19 @@ def wide_case(model, N, legs, reps, dev, d, raw_model=None):
         def p90(v):
             return sorted(v)[int(0.9 * (len(v) - 1))]
 
-        row = {"what": "wide: " + ("RAW 9-bit, one wide group push per tick" if leg == "r" else
+        row = {"what": "wide: " + ("fed PCM: one front-end launch, then one wide group push per tick" if leg == "p" else
+                                   "RAW 9-bit, one wide group push per tick" if leg == "r" else
                                    "one wide group push per tick" if wide else "ceil(N / 8) narrow group pushes per tick"),
                "leg": leg, "sessions": N, "frames": T, "chunk_frames": c, "audio_ms_per_tick": round(audio_ms, 2),
                "ticks_measured": len(full[0]), "tick_wall_ms_median": stat(0, med), "tick_wall_ms_p90": stat(0, p90),
                "tick_wall_ms_max": stat(0, max), "tick_device_ms_median": stat(1, med),
                "launches_per_tick": full[0][0][3], "reps": reps}
-        if wide:
+        wall[leg] = row["tick_wall_ms_median"]
+        if leg == "p":
+            row["tick_front_end_host_ms_median"] = stat(2, med)
+            if "b" in wall:
+                row["tick_wall_ms_over_mel_fed"] = round(wall["p"] - wall["b"], 3)
+        elif wide:
             row["tick_loop_ms_median"] = loop_ms[leg] = stat(2, med)
             row["tick_conditioning_ms_median"] = round(med(med(t[1] - t[2] for t in ticks) for ticks in full), 3)
         row["x_real_time"] = round(N * audio_ms / row["tick_wall_ms_median"], 1)
@@ -365,6 +425,8 @@ def main():
                     help="--wide: a = narrow group pushes (runs on older libraries too), b = one wide group push")
     ap.add_argument("--raw", action="store_true",
                     help="--wide: add leg r, the wide leg on the RAW 9-bit rnn / fc 512 model")
+    ap.add_argument("--audio", action="store_true",
+                    help="--wide: add leg p, the wide leg fed PCM through the mel front end (push_audio's path)")
     ap.add_argument("--rows", nargs="+", choices=sorted(ROWS_MODELS), default=[], metavar="MODEL",
                     help="only the rows-session case, for each model: " + ", ".join(sorted(ROWS_MODELS)))
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
@@ -395,7 +457,7 @@ def main():
             raw_model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(dr, 0).items()})
             raw_model.eval()
         for n in args.wide:
-            wide_case(model, n, args.legs, args.reps, dev, d, raw_model)
+            wide_case(model, n, args.legs, args.reps, dev, d, raw_model, args.audio)
         model.train()
         return
     mel = torch.from_numpy(syn.make_mel(d.feat_dims, args.frames, seed=1))[None].to(dev)

@@ -25,11 +25,19 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_list_plan", "wrnn_generate_list", "wrnn_stream_open_wide", "wrnn_wide_plan",
            "wrnn_stream_mu_law", "wrnn_wide_steps_per_launch", "wrnn_list_wide_plan", "wrnn_generate_list_wide",
            "wrnn_postprocess_list", "wrnn_list_folds_plan", "wrnn_generate_list_folds", "wrnn_postprocess_list_folds",
-           "wrnn_stream_open_rows", "wrnn_upsample_pack_window", "wrnn_upsample_window_frames")
+           "wrnn_stream_open_rows", "wrnn_upsample_pack_window", "wrnn_upsample_window_frames",
+           "wrnn_melspec_frames", "wrnn_melspec_table_floats", "wrnn_melspec_tables", "wrnn_melspec",
+           "wrnn_melspec_window", "wrnn_melspec_windows", "wrnn_melspec_plan")
+MELSPEC_SCRATCH_PER_SIGNAL = 64
 
 
 class MelResNetCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("in_dims", "compute_dims", "res_out_dims", "res_blocks", "pad")]
+
+
+class MelSpecCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("sample_rate", "n_fft", "hop_length", "win_length", "num_mels")] + \
+        [("fmin", ctypes.c_float), ("min_level_db", ctypes.c_float)]
 
 
 class WrnnError(RuntimeError):
@@ -178,6 +186,26 @@ def lib() -> ctypes.CDLL:
     L.wrnn_postprocess_list_folds.restype = i32
     L.wrnn_fingerprint.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i64), i32, vp, vp]
     L.wrnn_fingerprint.restype = i32
+    pms, pi64 = ctypes.POINTER(MelSpecCfg), ctypes.POINTER(i64)
+    L.wrnn_melspec_frames.argtypes = [pms, i64]
+    L.wrnn_melspec_frames.restype = i64
+    L.wrnn_melspec_table_floats.argtypes = [pms]
+    L.wrnn_melspec_table_floats.restype = i32
+    L.wrnn_melspec_tables.argtypes = [pms, vp]
+    L.wrnn_melspec_tables.restype = i32
+    # cfg, tables, wav pointers [U], n [U], U, mel pointers [U], ld [U], scratch, stream
+    L.wrnn_melspec.argtypes = [pms, vp, ctypes.POINTER(vp), pi, i32, ctypes.POINTER(vp), pi, vp, vp]
+    L.wrnn_melspec.restype = i32
+    # cfg, tables, wav_tail, s0, ns, total (−1: unknown), t0, nt, mel, ld, scratch, stream
+    L.wrnn_melspec_window.argtypes = [pms, vp, vp, i64, i32, i64, i32, i32, vp, i32, vp, vp]
+    L.wrnn_melspec_window.restype = i32
+    # the same with arrays of U entries (U after nt)
+    L.wrnn_melspec_windows.argtypes = [pms, vp, ctypes.POINTER(vp), pi64, pi, pi64, pi, pi, i32, ctypes.POINTER(vp), pi,
+                                       vp, vp]
+    L.wrnn_melspec_windows.restype = i32
+    # cfg, received, final → frames_ready, keep_from
+    L.wrnn_melspec_plan.argtypes = [pms, i64, i32, pi64, pi64]
+    L.wrnn_melspec_plan.restype = i32
     L.wrnn_cond_last_error.argtypes = []
     L.wrnn_cond_last_error.restype = ctypes.c_char_p
     _lib = L

@@ -1,7 +1,10 @@
 """Audio helpers of the reference's utils/dsp.py: everything generate(), gen_wavernn.py and the
 training data path touch without librosa (mu-law, labels, 16-bit split, wav I/O, dB scaling,
-emphasis filters).  Feature extraction (STFT/mel, Griffin-Lim) is preprocessing and out
-of scope."""
+emphasis filters), and its melspectrogram(): on a GPU the HIP kernel of csrc/melspec.hip, without
+one a float32 numpy/scipy path of the same definition.  That definition is librosa's published
+one restated (pinned to tests/melspec_ref.py, not to librosa's output, which no
+build of this project can run).  Griffin-Lim and spectrogram() stay out of scope (SURVEY.md §2
+row 4)."""
 from __future__ import annotations
 
 import math
@@ -112,3 +115,91 @@ def de_emphasis(x, preemphasis: float = 0.97):
     """utils/dsp.py:88-89 (the inverse IIR)."""
     from scipy.signal import lfilter
     return lfilter([1], [1, -preemphasis], x)
+
+
+# ------------------------------------------------------------------ mel front end (utils/dsp.py:41-81)
+MELSPEC_KEYS = ("sample_rate", "n_fft", "hop_length", "win_length", "num_mels", "fmin", "min_level_db")
+
+
+def melspec_params(hp=None, **overrides) -> dict:
+    """The front end's seven parameters from an HParams, a mapping or None (hparams.DEFAULTS)."""
+    from .hparams import DEFAULTS
+    out = {k: DEFAULTS[k] for k in MELSPEC_KEYS}
+    if hp is not None:
+        for k in MELSPEC_KEYS:
+            if isinstance(hp, dict):
+                out[k] = hp.get(k, out[k])
+            else:
+                out[k] = getattr(hp, k, out[k])
+    out.update({k: v for k, v in overrides.items() if v is not None})
+    return out
+
+
+def stft_window(n_fft: int = 2048, win_length: int = 1100) -> np.ndarray:
+    """float64 [n_fft]: scipy.signal.get_window('hann', win_length, fftbins=True) (periodic), centred
+    in n_fft as librosa's pad_center does: (n_fft − win_length)//2 zeros on the left."""
+    n = np.arange(win_length, dtype=np.float64)
+    left = (n_fft - win_length) // 2
+    return np.pad(0.5 - 0.5 * np.cos(2.0 * np.pi * n / win_length), (left, n_fft - win_length - left))
+
+
+def _hz_to_mel(f):
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f < 1000.0, f / (200.0 / 3.0), 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0))
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m < 15.0, (200.0 / 3.0) * m, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)))
+
+
+def mel_basis(sample_rate: int = 22050, n_fft: int = 2048, num_mels: int = 80, fmin: float = 40.0) -> np.ndarray:
+    """float64 [num_mels][n_fft//2 + 1]: librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax=sr/2,
+    htk=False, norm='slaney') from its definition — triangles between num_mels + 2 points equally
+    spaced on the Slaney mel scale, each scaled by 2 / (its width in Hz)."""
+    fmax = sample_rate / 2.0
+    mf = _mel_to_hz(np.linspace(_hz_to_mel(fmin), _hz_to_mel(fmax), num_mels + 2))
+    freqs = np.linspace(0.0, fmax, n_fft // 2 + 1)
+    fdiff = np.diff(mf)
+    ramps = mf[:, None] - freqs[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    return np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (mf[2:] - mf[:-2]))[:, None]
+
+
+def melspec_frames(n_samples: int, hop_length: int = 275) -> int:
+    return 1 + int(n_samples) // int(hop_length)
+
+
+def _melspectrogram_host(y: np.ndarray, p: dict) -> np.ndarray:
+    """The definition in float32 on the host (scipy.fft keeps single precision)."""
+    import scipy.fft
+    n_fft, hop = int(p["n_fft"]), int(p["hop_length"])
+    y = np.asarray(y, dtype=np.float32)
+    if y.ndim != 1 or len(y) < n_fft // 2 + 1:
+        raise ValueError(f"melspectrogram needs a 1-D signal of at least n_fft//2 + 1 = {n_fft // 2 + 1} samples")
+    yp = np.pad(y, n_fft // 2, mode="reflect")
+    T = melspec_frames(len(y), hop)
+    frames = np.lib.stride_tricks.sliding_window_view(yp, n_fft)[::hop][:T]
+    D = np.abs(scipy.fft.rfft(frames * stft_window(n_fft, int(p["win_length"])).astype(np.float32), axis=1))
+    W = mel_basis(int(p["sample_rate"]), n_fft, int(p["num_mels"]), float(p["fmin"])).astype(np.float32)
+    S = W @ D.astype(np.float32).T
+    db = np.float32(20.0) * np.log10(np.maximum(np.float32(1e-5), S))
+    mdb = np.float32(p["min_level_db"])
+    return np.clip((db - mdb) / -mdb, 0, 1).astype(np.float32)
+
+
+def melspectrogram(y, hp=None, device=None) -> np.ndarray:
+    """utils/dsp.py:75-78: wav (1-D, float) → normalised mel float32 (num_mels, 1 + len(y)//hop), what
+    generate() and gen_wavernn's load_mel take.  `hp`: an HParams, a mapping, or None for the
+    defaults.  With a GPU (device None: when torch sees one) the HIP kernel computes it
+    (wavernn_amd.melspec.MelSpec); without one, or with device='cpu', the float32 host path of the
+    same definition.  The two agree to float32 rounding of the definition, not bit for bit."""
+    p = melspec_params(hp)
+    if device is None:
+        import torch
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    if str(device).startswith("cpu"):
+        return _melspectrogram_host(np.asarray(y), p)
+    from .melspec import MelSpec
+    return MelSpec.get(p, device).run([y])[0].cpu().numpy()

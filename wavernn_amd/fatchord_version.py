@@ -550,10 +550,44 @@ class WaveRNN(nn.Module):
         self.train()
         return outputs
 
+    # --------------------------------------------------------------------- wav input
+    def _front(self, hp=None):
+        """The mel front end for this model (wavernn_amd.melspec.MelSpec): hop_length, sample_rate and
+        num_mels are the model's; n_fft, win_length, fmin and min_level_db come from `hp` (an HParams
+        or a mapping) or the reference's defaults."""
+        from .melspec import MelSpec
+        device = next(self.parameters()).device
+        if device.type != 'cuda':
+            raise RuntimeError("WaveRNN.melspectrogram runs on the MI355X HIP path: move the model to a GPU "
+                               "(model.to('cuda')); dsp.melspectrogram(device='cpu') is the host path")
+        p = dsp.melspec_params(hp, hop_length=self.hop_length, sample_rate=self.sample_rate, num_mels=self.feat_dims)
+        return MelSpec.get(p, device)
+
+    @torch.no_grad()
+    def melspectrogram(self, wavs, hp=None) -> List[torch.Tensor]:
+        """utils/dsp.py:75-78 on the GPU (C-ABI wrnn_melspec, csrc/melspec.hip): `wavs` is a 1-D
+        signal, a [U][n] tensor, or a list of 1-D tensors / arrays of unequal length (float, the
+        model's sample rate) → a list of device mels (1, num_mels, 1 + n_u // hop) from ONE launch,
+        ready for generate, generate_many and generate_list."""
+        if isinstance(wavs, (torch.Tensor, np.ndarray)):
+            wavs = [wavs] if wavs.ndim == 1 else list(wavs)
+        return [m[None] for m in self._front(hp).run(list(wavs))]
+
+    def generate_from_wav(self, wav, save_path: Union[str, Path, None], batched, target, overlap, mu_law, *,
+                          hp=None, **kw):
+        """Copy synthesis (gen_wavernn.py --file x.wav): melspectrogram(wav), then generate() as it is;
+        keywords go to generate()."""
+        return self.generate(self.melspectrogram(wav, hp)[0], save_path, batched, target, overlap, mu_law, **kw)
+
+    def generate_list_from_wavs(self, wavs: Sequence, save_paths: Optional[Sequence] = None, *, hp=None, **kw):
+        """melspectrogram(wavs) (one launch for the whole list), then generate_list() as it is."""
+        return self.generate_list(self.melspectrogram(wavs, hp), save_paths, **kw)
+
     # --------------------------------------------------------------------- streaming
     def stream(self, n_streams: int = 1, total_frames: Optional[int] = None, *, noise=None,
                seed: Optional[int] = None, row_offset: int = 0, wide: bool = False,
-               mu_law: bool = True, rows: bool = False) -> "WaveRNNStream":
+               mu_law: bool = True, rows: bool = False, total_samples: Optional[int] = None,
+               hp=None) -> "WaveRNNStream":
         """A streaming session: push mel frames as the acoustic model produces them, get the audio
         that has become final — unbatched MoL generate() in pieces, the recurrent state kept on the
         GPU between pushes (C-ABI wrnn_stream_*).  `n_streams` utterances (1..8) advance in lock
@@ -595,8 +629,18 @@ class WaveRNN(nn.Module):
         is [steps][n_streams][11] for MoL and [steps][n_streams][n_classes] Exp(1) draws for RAW;
         `mu_law` as for wide RAW sessions.  With the same draws the session's samples are those of
         generate() on the multi-row kernel (WRNN_PATH=rows).  A rows session advances alone
-        (push_streams refuses it), and `rows=True, wide=True` is a ValueError."""
-        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset, wide, mu_law, rows)
+        (push_streams refuses it), and `rows=True, wide=True` is a ValueError.
+
+        Audio in: a session of any kind also takes PCM — push_audio(pcm) / finish_audio() run the mel
+        front end (melspectrogram's kernel, `hp` its geometry) on the frames that became final and
+        hand them to push().  `total_samples=` in place of `total_frames=` states the length in
+        samples (1 + total_samples // hop frames)."""
+        if total_samples is not None:
+            if total_frames is not None:
+                raise ValueError("give total_frames or total_samples, not both")
+            total_frames = 1 + int(total_samples) // self.hop_length
+        return WaveRNNStream(self, n_streams, total_frames, noise, seed, row_offset, wide, mu_law, rows,
+                             total_samples=total_samples, hp=hp)
 
     def push_streams(self, pushes) -> list:
         """Advance several sessions of this model in one call: `pushes` is a sequence of
@@ -610,19 +654,43 @@ class WaveRNN(nn.Module):
         session that leaves seven XCDs idle.  The members' rows together are at most 8; a finished
         session is no longer listed.  Refusals raise ValueError and leave every member unchanged.
         A group whose members were all opened with wide=True may hold up to 128 rows (16 per XCD,
-        one persistent launch per round of equal step counts); wide and narrow members do not mix."""
-        members = []
+        one persistent launch per round of equal step counts); wide and narrow members do not mix.
+        A member may also be (WaveRNNStream, pcm): an audio push, what stream.push_audio(pcm) returns;
+        the new mel frames of all such members come from one front-end launch (C-ABI
+        wrnn_melspec_windows) before the group push.  A member ends its audio with finish_audio()."""
+        members, audio = [], []
         for item in pushes:
-            if not isinstance(item, (tuple, list)) or len(item) != 3 or not isinstance(item[0], WaveRNNStream):
-                raise ValueError("pushes holds (WaveRNNStream, mel_chunk or None, final) tuples")
-            s, mel, final = item
-            if s._model is not self:
+            if not isinstance(item, (tuple, list)) or len(item) not in (2, 3) or not isinstance(item[0], WaveRNNStream) \
+                    or (len(item) == 2 and item[1] is None):   # an audio push brings samples
+                raise ValueError("pushes holds (WaveRNNStream, mel_chunk or None, final) or (WaveRNNStream, pcm) tuples")
+            if item[0]._model is not self:
                 raise ValueError("a member session belongs to another model")
-            members.append((s._session, s._mel_tensor(mel), bool(final)))
+            if len(item) == 2:
+                audio.append((len(members), item[0], item[0]._audio_feed().stage(item[1])))
+                members.append(None)
+            else:
+                s, mel, final = item
+                members.append((s._session, s._mel_tensor(mel), bool(final)))
         if not members:
             raise ValueError("push_streams needs at least one member")
+        if audio:
+            # ONE front-end launch for the new frames of all audio members of one geometry (sessions
+            # opened with another hp= have their own tables: a launch each), then the group push as it is
+            fronts = {}
+            for i, s, (_, js, _) in audio:
+                fronts.setdefault(s._audio_feed().front, []).append((i, s, js))
+            for front, group in fronts.items():
+                jobs = [j for _, _, js in group for j in js]
+                mels = front.windows(jobs) if jobs else []
+                at = 0
+                for i, s, js in group:
+                    members[i] = (s._session, torch.stack(mels[at:at + len(js)]) if js else None, False)
+                    at += len(js)
         # the members' own loop, as it is: a push does not look at the weights (WaveRNN.stream)
-        return [w.cpu().numpy() for w in members[0][0].loop.push_streams(members)]
+        waves = [w.cpu().numpy() for w in members[0][0].loop.push_streams(members)]
+        for _, s, (state, _, _) in audio:   # a refusal raised above: no audio member has changed
+            s._audio_feed().commit(state)
+        return waves
 
     def generate_stream(self, mels, chunk_frames: int = 8, *, noise=None, seed: Optional[int] = None,
                         row_offset: int = 0, wide: bool = False, mu_law: bool = True, rows: bool = False):
@@ -752,9 +820,12 @@ class WaveRNNStream:
     WaveRNN.push_streams advances several sessions in one call, each at its own pace."""
 
     def __init__(self, model: WaveRNN, n_streams: int, total_frames: Optional[int], noise, seed: Optional[int],
-                 row_offset: int, wide: bool = False, mu_law: bool = True, rows: bool = False):
+                 row_offset: int, wide: bool = False, mu_law: bool = True, rows: bool = False, *,
+                 total_samples: Optional[int] = None, hp=None):
         if rows and wide:
             raise ValueError("rows=True and wide=True name two kernels: a session runs on one")
+        # audio in (push_audio / finish_audio): the signal's length when known, the front end's geometry
+        self._total_samples, self._hp, self._feed = total_samples, hp, None
         if wide and not 1 <= int(n_streams) <= 128:
             raise ValueError(f"a wide session has 1..128 utterances, not {n_streams!r}")
         device = next(model.parameters()).device
@@ -794,6 +865,34 @@ class WaveRNNStream:
 
     def finish(self) -> np.ndarray:
         return self._session.push(None, final=True).cpu().numpy()
+
+    # audio in: the mel front end in front of push()
+    def _audio_feed(self):
+        if self._feed is None:
+            from .melspec import AudioFeed
+            self._feed = AudioFeed(self._model._front(self._hp), self.n_streams, self._total_samples)
+        return self._feed
+
+    def push_audio(self, pcm) -> np.ndarray:
+        """PCM in ([n], or [U][n] for U streams in lock step; float, the model's sample rate): the mel
+        frames that became final with these samples (wrnn_melspec_plan) are computed on the GPU from
+        the session's PCM tail (wrnn_melspec_windows) and pushed → what push() returns for them,
+        float64 [U][m] (m = 0 while no frame is final).  The frames are bit-identical to
+        melspectrogram() of the whole signal, however the samples were cut into pushes."""
+        feed = self._audio_feed()
+        state, jobs, nt = feed.stage(pcm)
+        out = self.push(torch.stack(feed.front.windows(jobs))) if nt else np.zeros((self.n_streams, 0))
+        feed.commit(state)
+        return out
+
+    def finish_audio(self) -> np.ndarray:
+        """The signal has ended: its remaining frames (the right edge reflected now that the length is
+        known) are pushed and the session finished → the rest of the audio."""
+        feed = self._audio_feed()
+        state, jobs, nt = feed.stage(None, final=True)
+        out = [self.push(torch.stack(feed.front.windows(jobs)))] if nt else []
+        feed.commit(state)
+        return np.concatenate(out + [self.finish()], axis=1)
 
     def close(self) -> None:
         self._session.close()
