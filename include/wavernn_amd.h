@@ -787,6 +787,64 @@ int wrnn_melspec_windows(const wrnn_melspec_cfg *cfg, const float *tables, const
 int wrnn_melspec_plan(const wrnn_melspec_cfg *cfg, int64_t received, int final, int64_t *frames_ready,
                       int64_t *keep_from);
 
+/* ---- Tacotron decoder loop (csrc/tacotron_decoder.hip) --------------------------------
+ * The reference's Decoder.forward / LSA.forward in eval mode (models/tacotron.py:171-286) and the
+ * loop and stop rule of Tacotron.generate (:453-461), for 1..128 rows (one row = one sentence) in
+ * ONE persistent launch: prenet on the previous step's last frame, attention GRU cell, LSA (scores =
+ * sigmoid(u) / sum sigmoid(u) over the row's own t_enc positions), context, rnn_input, two residual
+ * LSTM cells, the r needed rows of mel_proj per mel, and the stop test (every one of the step's
+ * n_mels·r values < stop_threshold and step·r > 10; the stopping step's frames are kept).
+ * fp32 weights read in place (device pointers to the module's own contiguous tensors, PyTorch
+ * layouts), fp32 accumulation; a row's arithmetic does not depend on the other rows or on its slot.
+ * Stateless: errors leave their text in wrnn_cond_last_error.  Only the sizes below are taken;
+ * anything else is WRNN_EUNSUPPORTED. */
+typedef struct {
+    int32_t n_mels;        /* 80  */
+    int32_t decoder_dims;  /* 256 */
+    int32_t lstm_dims;     /* 512 */
+    int32_t encoder_dims;  /* 256: channels of encoder_seq (= decoder_dims in the reference) */
+    int32_t prenet_fc1;    /* 256 */
+    int32_t prenet_fc2;    /* 128 */
+    int32_t lsa_filters;   /* 32  */
+    int32_t lsa_kernel;    /* 31  */
+    int32_t max_r;         /* 20  */
+} wrnn_taco_cfg;
+
+/* Device pointers, every one required; shapes as in the reference's state_dict. */
+typedef struct {
+    const float *prenet_fc1_w, *prenet_fc1_b, *prenet_fc2_w, *prenet_fc2_b;
+    const float *attn_rnn_w_ih, *attn_rnn_w_hh, *attn_rnn_b_ih, *attn_rnn_b_hh;
+    const float *lsa_conv_w, *lsa_L_w, *lsa_L_b, *lsa_W_w, *lsa_W_b, *lsa_v;
+    const float *rnn_input_w, *rnn_input_b;
+    const float *res_rnn1_w_ih, *res_rnn1_w_hh, *res_rnn1_b_ih, *res_rnn1_b_hh;
+    const float *res_rnn2_w_ih, *res_rnn2_w_hh, *res_rnn2_b_ih, *res_rnn2_b_hh;
+    const float *mel_proj_w;
+} wrnn_taco_weights;
+
+/* WRNN_OK when the kernel takes these sizes, else WRNN_EUNSUPPORTED with the reason. */
+int wrnn_taco_supported(const wrnn_taco_cfg *cfg);
+/* The recurrent state is a caller-owned device buffer of rows × wrnn_taco_state_floats(cfg, t_max)
+ * floats; a fresh sentence starts from all zeros.  wrnn_taco_state_layout fills the offset (in
+ * floats, within a row) of each field, in this order: attn_hidden [decoder_dims], rnn1_hidden,
+ * rnn1_cell, rnn2_hidden, rnn2_cell [lstm_dims each], context [decoder_dims], cumulative [t_max],
+ * attention [t_max], last frame [n_mels], step (int32: decoder steps done), stopped (int32: 0 / 1).
+ * The caller may read and write any of it between calls (tests start from recorded states). */
+#define WRNN_TACO_STATE_FIELDS 11
+int wrnn_taco_state_floats(const wrnn_taco_cfg *cfg, int t_max);
+int wrnn_taco_state_layout(const wrnn_taco_cfg *cfg, int t_max, int32_t *offsets);
+int64_t wrnn_taco_scratch_floats(const wrnn_taco_cfg *cfg, int rows);
+/* Runs up to n_steps further decoder steps of every row that has not stopped and whose step counter
+ * is below step_cap (= ceil(steps / r)); the launch ends early once no such row is left.  Row b reads
+ * enc / enc_proj [rows][t_max][encoder_dims] at its first t_enc[b] positions (device int32, each in
+ * 1..t_max) and writes step s to mel [rows][step_cap·r][n_mels] (frames s·r .. s·r + r − 1) and attn
+ * [rows][step_cap][t_max] (first t_enc[b] entries); a stopped row writes nothing further.  The step
+ * counts come back in the state.  Synchronises `stream`.  Every inter-workgroup wait is bounded by
+ * timeout_ms (0: 2000): a missed hand-off is WRNN_ETIMEOUT, never a hang.  WRNN_EUNSUPPORTED on a
+ * device with fewer than 128 CUs (one workgroup per CU, all co-resident, one owner per row). */
+int wrnn_taco_run(const wrnn_taco_cfg *cfg, const wrnn_taco_weights *w, const float *enc, const float *enc_proj,
+                  const int32_t *t_enc, int t_max, int rows, int r, float stop_threshold, int step_cap, int n_steps,
+                  float *state, float *mel, float *attn, float *scratch, int timeout_ms, void *stream);
+
 /* Message of the last failed stateless call on this thread. */
 const char *wrnn_cond_last_error(void);
 

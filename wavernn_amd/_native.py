@@ -27,7 +27,8 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_postprocess_list", "wrnn_list_folds_plan", "wrnn_generate_list_folds", "wrnn_postprocess_list_folds",
            "wrnn_stream_open_rows", "wrnn_upsample_pack_window", "wrnn_upsample_window_frames",
            "wrnn_melspec_frames", "wrnn_melspec_table_floats", "wrnn_melspec_tables", "wrnn_melspec",
-           "wrnn_melspec_window", "wrnn_melspec_windows", "wrnn_melspec_plan")
+           "wrnn_melspec_window", "wrnn_melspec_windows", "wrnn_melspec_plan", "wrnn_taco_supported",
+           "wrnn_taco_state_floats", "wrnn_taco_state_layout", "wrnn_taco_scratch_floats", "wrnn_taco_run")
 MELSPEC_SCRATCH_PER_SIGNAL = 64
 
 
@@ -38,6 +39,23 @@ class MelResNetCfg(ctypes.Structure):
 class MelSpecCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("sample_rate", "n_fft", "hop_length", "win_length", "num_mels")] + \
         [("fmin", ctypes.c_float), ("min_level_db", ctypes.c_float)]
+
+
+TACO_WEIGHTS = ("prenet_fc1_w", "prenet_fc1_b", "prenet_fc2_w", "prenet_fc2_b", "attn_rnn_w_ih", "attn_rnn_w_hh",
+                "attn_rnn_b_ih", "attn_rnn_b_hh", "lsa_conv_w", "lsa_L_w", "lsa_L_b", "lsa_W_w", "lsa_W_b", "lsa_v",
+                "rnn_input_w", "rnn_input_b", "res_rnn1_w_ih", "res_rnn1_w_hh", "res_rnn1_b_ih", "res_rnn1_b_hh",
+                "res_rnn2_w_ih", "res_rnn2_w_hh", "res_rnn2_b_ih", "res_rnn2_b_hh", "mel_proj_w")
+TACO_STATE_FIELDS = ("attn_hidden", "rnn1_hidden", "rnn1_cell", "rnn2_hidden", "rnn2_cell", "context", "cumulative",
+                     "attention", "frame", "step", "stopped")
+
+
+class TacoCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_mels", "decoder_dims", "lstm_dims", "encoder_dims", "prenet_fc1",
+                                              "prenet_fc2", "lsa_filters", "lsa_kernel", "max_r")]
+
+
+class TacoWeights(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in TACO_WEIGHTS]
 
 
 class WrnnError(RuntimeError):
@@ -206,6 +224,20 @@ def lib() -> ctypes.CDLL:
     # cfg, received, final → frames_ready, keep_from
     L.wrnn_melspec_plan.argtypes = [pms, i64, i32, pi64, pi64]
     L.wrnn_melspec_plan.restype = i32
+    ptc, f32 = ctypes.POINTER(TacoCfg), ctypes.c_float
+    L.wrnn_taco_supported.argtypes = [ptc]
+    L.wrnn_taco_supported.restype = i32
+    L.wrnn_taco_state_floats.argtypes = [ptc, i32]
+    L.wrnn_taco_state_floats.restype = i32
+    L.wrnn_taco_state_layout.argtypes = [ptc, i32, pi]
+    L.wrnn_taco_state_layout.restype = i32
+    L.wrnn_taco_scratch_floats.argtypes = [ptc, i32]
+    L.wrnn_taco_scratch_floats.restype = i64
+    # cfg, weights, enc, enc_proj, t_enc, t_max, rows, r, stop_threshold, step_cap, n_steps, state, mel, attn, scratch,
+    # timeout_ms, stream
+    L.wrnn_taco_run.argtypes = [ptc, ctypes.POINTER(TacoWeights), vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp,
+                                i32, vp]
+    L.wrnn_taco_run.restype = i32
     L.wrnn_cond_last_error.argtypes = []
     L.wrnn_cond_last_error.restype = ctypes.c_char_p
     _lib = L

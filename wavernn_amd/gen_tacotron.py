@@ -8,21 +8,29 @@ The reference synthesises each sentence with its PyTorch Tacotron and hands the 
     m = torch.tensor(m).unsqueeze(0)                  # :167
     voc_model.generate(m, save_path, batched, hp.voc_target, hp.voc_overlap, hp.mu_law)   # :168
 
-Tacotron, the text front-end and Griffin-Lim stay outside this package (SURVEY.md §8(f)3:
-"Tacotron stays PyTorch"): `synthesize()` takes any object with the reference Tacotron's
-`generate(x) -> (linear, mel, attention)` and any sequence of already-encoded inputs
-(`text_to_sequence` output), so the reference's own Tacotron drops in unchanged. The CLI vocodes
-mels that a Tacotron run saved as .npy (Tacotron scale, before the :147 rescale):
+The text front-end and Griffin-Lim stay outside this package: `synthesize()` takes any object
+with the reference Tacotron's `generate(x)` triple and any sequence of already-encoded inputs
+(`text_to_sequence` output), so `wavernn_amd.tacotron.Tacotron` (decoder loop on the GPU) and the
+reference's own PyTorch Tacotron both drop in. `synthesize_list()` runs all sentences at once:
+`tts_model.generate_list` → the same rescale → `voc_model.generate_list(wide=True)`. The CLI
+vocodes mels that a Tacotron run saved as .npy (Tacotron scale, before the :147 rescale), or
+synthesises encoded sentences from a Tacotron checkpoint:
 
     python -m wavernn_amd.gen_tacotron -m mel0.npy mel1.npy [-b|-u] [-t T] [-o O]
                                        [--voc_weights W.pyt] [--hp_file hparams.py]
                                        [--tts_k K] [--out_dir DIR] [--names a b ...]
+    python -m wavernn_amd.gen_tacotron --tts_weights T.pyt --sequences ids.txt|ids.npy [...]
+
+`--sequences` is a .npy of integer ids (1-D: one sentence; 2-D: one sentence per row) or a text file
+with one line of integer ids per sentence. With `--sequences` the sentences go through
+`synthesize_list` (the unbatched wide vocoder list): -b / -u, --target and --overlap do not apply and
+are refused.
 """
 from __future__ import annotations
 
 import argparse
 from pathlib import Path
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -78,6 +86,51 @@ def synthesize(tts_model, voc_model, inputs: Sequence, out_dir: Path, batched: b
     return wavs
 
 
+def synthesize_list(tts_model, voc_model, inputs: Sequence, out_dir: Optional[Path] = None, tts_k: int = 0,
+                    standard_names: Optional[Sequence[str]] = None, seed: Optional[int] = None, steps: int = 2000,
+                    save_attention: Optional[Callable] = None) -> List[np.ndarray]:
+    """All sentences at once: `tts_model.generate_list(inputs)` (one decoder launch per 128
+    sentences), the :147-148 rescale of the second returned array as the reference takes it, then
+    `voc_model.generate_list(mels, wide=True)`. With `out_dir` the waveforms are saved under the
+    names `synthesize()` would give them. Returns the waveforms in the order of `inputs`."""
+    from .dsp import save_wav
+    triples = tts_model.generate_list(list(inputs), steps=steps)
+    mels = [tacotron_mel_to_vocoder(m) for _, m, _ in triples]
+    wavs = voc_model.generate_list(mels, seed=seed, wide=True)
+    if out_dir is not None:
+        out_dir = Path(out_dir)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        for i, (w, (_, _, attention)) in enumerate(zip(wavs, triples), 1):
+            name = output_name(i, 'wavernn_list', tts_k, None, standard_names[i - 1] if standard_names else None)
+            if save_attention is not None:
+                save_attention(attention, out_dir / name)
+            save_wav(np.asarray(w), out_dir / name)
+    return wavs
+
+
+def load_sequences(path: Union[str, Path]) -> List[np.ndarray]:
+    """`--sequences FILE`: a .npy of ids (1-D: one sentence; 2-D: one per row) or a text file with one
+    line of integer ids (blank- or comma-separated) per sentence."""
+    p = Path(path)
+    if p.suffix == '.npy':
+        a = np.load(p, allow_pickle=False)
+        if a.ndim not in (1, 2) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f'Expected a 1-D or 2-D integer array of symbol ids, but got {a.dtype} {a.shape}!')
+        return [np.asarray(r, dtype=np.int64) for r in (a[None] if a.ndim == 1 else a)]
+    seqs = []
+    for n, line in enumerate(p.read_text().splitlines(), 1):
+        line = line.replace(',', ' ').strip()
+        if not line:
+            continue
+        try:
+            seqs.append(np.array([int(t) for t in line.split()], dtype=np.int64))
+        except ValueError:
+            raise ValueError(f'{p}:{n}: expected integer symbol ids') from None
+    if not seqs:
+        raise ValueError(f'{p} holds no sentence')
+    return seqs
+
+
 class _SavedMels:
     """Stands in for Tacotron when its mels were saved to disk: generate(i) → (None, mel, None)."""
 
@@ -97,7 +150,10 @@ class _SavedMels:
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Vocode Tacotron mels on MI355X (gen_tacotron.py, wavernn branch)')
-    ap.add_argument('--mels', '-m', nargs='+', required=True, help='Tacotron mel .npy files (Tacotron scale)')
+    ap.add_argument('--mels', '-m', nargs='+', help='Tacotron mel .npy files (Tacotron scale)')
+    ap.add_argument('--tts_weights', type=str, help='reference-format Tacotron state_dict (*.pyt)')
+    ap.add_argument('--sequences', metavar='FILE', help='encoded sentences: .npy, or one line of ids per sentence (vocoded as one unbatched wide list; '
+                         'not with -b / -u / -t / -o)')
     ap.add_argument('--batched', '-b', dest='batched', action='store_true', help='Fast Batched Generation')
     ap.add_argument('--unbatched', '-u', dest='batched', action='store_false', help='Slow Unbatched Generation')
     ap.add_argument('--overlap', '-o', type=int)
@@ -114,14 +170,28 @@ def main(argv=None):
     target = args.target if args.target is not None else hp.voc_target
     overlap = args.overlap if args.overlap is not None else hp.voc_overlap
     batched = args.batched if args.batched is not None else hp.voc_gen_batched
-    if args.names is not None and len(args.names) != len(args.mels):
-        raise ValueError('--names needs one name per mel')
+    if (args.mels is None) == (args.sequences is None):
+        ap.error('give either --mels or --sequences')
+    if args.sequences is not None and not args.tts_weights:
+        ap.error('--sequences needs --tts_weights')
+    if args.sequences is not None and (args.batched is not None or args.target is not None or args.overlap is not None):
+        ap.error('--sequences vocodes through the unbatched wide list: -b / -u, --target and --overlap do not apply')
+    seqs = load_sequences(args.sequences) if args.sequences is not None else None
+    if args.names is not None and len(args.names) != len(args.mels if seqs is None else seqs):
+        raise ValueError('--names needs one name per ' + ('mel' if seqs is None else 'sentence'))
     if not torch.cuda.is_available():
         raise RuntimeError('the MI355X generation path needs a GPU')
     from .gen_wavernn import build_model
     voc = build_model(hp, torch.device('cuda'))
     if args.voc_weights:
         voc.load(args.voc_weights)
+    if seqs is not None:
+        from .tacotron import build_tacotron
+        tts = build_tacotron(hp, weights=args.tts_weights, device=torch.device('cuda'))
+        synthesize_list(tts, voc, seqs, Path(args.out_dir), tts_k=args.tts_k or tts.get_step() // 1000,
+                        standard_names=args.names, seed=args.seed)
+        print('\n\nDone.\n')
+        return
     tts = _SavedMels(args.mels, hp.num_mels)
     synthesize(tts, voc, list(range(len(args.mels))), Path(args.out_dir), batched, target, overlap, hp.mu_law,
                tts_k=args.tts_k, standard_names=args.names, seed=args.seed)

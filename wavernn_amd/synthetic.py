@@ -255,3 +255,146 @@ def make_dm_noise(B: int, L: int, Q: int = 256, seed: int = 3) -> np.ndarray:
     """Exp(1) draws [L][B][2·Q]: the coarse Categorical's q, then the fine one's, per step."""
     g = np.random.default_rng(seed)
     return g.exponential(1.0, size=(L, B, 2 * Q)).astype(np.float32)
+
+
+# ---------------------------------------------------------------------- tacotron
+@dataclass(frozen=True)
+class TacotronDims:
+    """Constructor arguments of models/tacotron.py:Tacotron (:290); the defaults are hparams.py:67-77
+    with the symbol table's size left to the caller."""
+    embed_dims: int = 256
+    num_chars: int = 148
+    encoder_dims: int = 128
+    decoder_dims: int = 256
+    n_mels: int = 80
+    fft_bins: int = 80
+    postnet_dims: int = 128
+    encoder_K: int = 16
+    lstm_dims: int = 512
+    postnet_K: int = 8
+    num_highways: int = 4
+    dropout: float = 0.5
+    stop_threshold: float = -3.4
+
+    def ctor_kwargs(self) -> dict:
+        return {k: getattr(self, k) for k in self.__dataclass_fields__}
+
+
+DEFAULT_TACOTRON = TacotronDims()
+
+
+def tacotron_state_shapes(d: TacotronDims) -> Dict[str, Tuple[tuple, str]]:
+    """Every state_dict key of the reference Tacotron → (shape, kind). Kinds: 'x' xavier matrix,
+    'xd' xavier matrix of the decoder (scaled), 'b' bias, bn_*, 'emb', and the scalar buffers."""
+    s: Dict[str, Tuple[tuple, str]] = {"step": ((1,), "step"), "stop_threshold": ((), "thr"), "decoder.r": ((), "r")}
+
+    def lin(p, o, i, bias=True, kind="x"):
+        s[p + ".weight"] = ((o, i), kind)
+        if bias:
+            s[p + ".bias"] = ((o,), "b")
+
+    def bnconv(p, i, o, k):
+        s[p + ".conv.weight"] = ((o, i, k), "x")
+        s[p + ".bnorm.weight"] = ((o,), "bn_w")
+        s[p + ".bnorm.bias"] = ((o,), "bn_b")
+        s[p + ".bnorm.running_mean"] = ((o,), "bn_rm")
+        s[p + ".bnorm.running_var"] = ((o,), "bn_rv")
+        s[p + ".bnorm.num_batches_tracked"] = ((), "nbt")
+
+    def cbhg(p, K, cin, ch, proj):
+        for k in range(1, K + 1):
+            bnconv(f"{p}.conv1d_bank.{k - 1}", cin, ch, k)
+        bnconv(p + ".conv_project1", K * ch, proj[0], 3)
+        bnconv(p + ".conv_project2", proj[0], proj[1], 3)
+        if proj[1] != ch:
+            lin(p + ".pre_highway", ch, proj[1], bias=False)
+        for i in range(d.num_highways):
+            lin(f"{p}.highways.{i}.W1", ch, ch)
+            lin(f"{p}.highways.{i}.W2", ch, ch)
+        for sfx in ("", "_reverse"):
+            s[f"{p}.rnn.weight_ih_l0{sfx}"] = ((3 * ch, ch), "x")
+            s[f"{p}.rnn.weight_hh_l0{sfx}"] = ((3 * ch, ch), "x")
+            s[f"{p}.rnn.bias_ih_l0{sfx}"] = ((3 * ch,), "b")
+            s[f"{p}.rnn.bias_hh_l0{sfx}"] = ((3 * ch,), "b")
+
+    D, H, M = d.decoder_dims, d.lstm_dims, d.n_mels
+    s["encoder.embedding.weight"] = ((d.num_chars, d.embed_dims), "emb")
+    lin("encoder.pre_net.fc1", 256, d.embed_dims)
+    lin("encoder.pre_net.fc2", 128, 256)
+    cbhg("encoder.cbhg", d.encoder_K, d.encoder_dims, d.encoder_dims, (d.encoder_dims, d.encoder_dims))
+    lin("encoder_proj", D, D, bias=False)
+    lin("decoder.prenet.fc1", 256, M, kind="xd")
+    lin("decoder.prenet.fc2", 128, 256, kind="xd")
+    s["decoder.attn_net.conv.weight"] = ((32, 2, 31), "xd")
+    lin("decoder.attn_net.L", D, 32, kind="xd")
+    lin("decoder.attn_net.W", D, D, kind="xd")
+    lin("decoder.attn_net.v", 1, D, bias=False, kind="xd")
+    s["decoder.attn_rnn.weight_ih"] = ((3 * D, D + D // 2), "xd")
+    s["decoder.attn_rnn.weight_hh"] = ((3 * D, D), "xd")
+    s["decoder.attn_rnn.bias_ih"] = ((3 * D,), "b")
+    s["decoder.attn_rnn.bias_hh"] = ((3 * D,), "b")
+    lin("decoder.rnn_input", H, 2 * D, kind="xd")
+    for n in ("res_rnn1", "res_rnn2"):
+        s[f"decoder.{n}.weight_ih"] = ((4 * H, H), "xd")
+        s[f"decoder.{n}.weight_hh"] = ((4 * H, H), "xd")
+        s[f"decoder.{n}.bias_ih"] = ((4 * H,), "b")
+        s[f"decoder.{n}.bias_hh"] = ((4 * H,), "b")
+    lin("decoder.mel_proj", M * 20, H, bias=False, kind="xd")
+    cbhg("postnet", d.postnet_K, M, d.postnet_dims, (256, 80))
+    lin("post_proj", d.fft_bins, 2 * d.postnet_dims, bias=False)
+    return s
+
+
+def make_tacotron_state(d: TacotronDims = DEFAULT_TACOTRON, seed: int = 0, scale: float = 1.0, r: int = 2,
+                        step: int = 180_000) -> Dict[str, np.ndarray]:
+    """Random Tacotron weights in the reference layout: matrices xavier-uniform (the reference's init),
+    biases U(±0.1), BatchNorm statistics in a plausible range, the embedding N(0, 1); the decoder's
+    matrices are multiplied by `scale` (1 tame, 2 lively, 3-4 saturated attention and gates). One
+    independent stream per key."""
+    shapes = tacotron_state_shapes(d)
+    out: Dict[str, np.ndarray] = {}
+    for key in sorted(shapes):
+        shape, kind = shapes[key]
+        g = _rng(seed, "taco:" + key)
+        if kind == "step":
+            out[key] = np.array([step], dtype=np.int64)
+        elif kind == "thr":
+            out[key] = np.array(d.stop_threshold, dtype=np.float32)
+        elif kind == "r":
+            out[key] = np.array(r, dtype=np.int32)
+        elif kind == "nbt":
+            out[key] = np.array(0, dtype=np.int64)
+        elif kind in ("x", "xd"):
+            rf = float(np.prod(shape[2:])) if len(shape) > 2 else 1.0
+            bound = np.sqrt(6.0 / ((shape[0] + shape[1]) * rf))
+            w = g.uniform(-bound, bound, size=shape)
+            out[key] = (w * (scale if kind == "xd" else 1.0)).astype(np.float32)
+        elif kind == "emb":
+            out[key] = g.standard_normal(shape).astype(np.float32)
+        elif kind == "b":
+            out[key] = g.uniform(-0.1, 0.1, size=shape).astype(np.float32)
+        elif kind == "bn_w":
+            out[key] = g.uniform(0.8, 1.2, size=shape).astype(np.float32)
+        elif kind == "bn_b":
+            out[key] = g.uniform(-0.1, 0.1, size=shape).astype(np.float32)
+        elif kind == "bn_rm":
+            out[key] = g.uniform(-0.2, 0.2, size=shape).astype(np.float32)
+        elif kind == "bn_rv":
+            out[key] = g.uniform(0.5, 1.5, size=shape).astype(np.float32)
+        else:  # pragma: no cover
+            raise ValueError(kind)
+    return out
+
+
+def make_text_ids(n: int, num_chars: int = 148, seed: int = 5) -> np.ndarray:
+    """n symbol ids in [1, num_chars) — a text_to_sequence output of length n."""
+    return np.random.default_rng([seed, n]).integers(1, num_chars, size=n).astype(np.int64)
+
+
+def make_encoder_seq(t_enc: int, dims: int = 256, seed: int = 7):
+    """(encoder_seq, encoder_seq_proj), each (t_enc, dims) float32: a biGRU-like output in (−1, 1) and an
+    independent projection-like array ~ 0.5·N(0, 1) — decoder inputs that need no encoder run."""
+    g = np.random.default_rng([seed, t_enc, dims])
+    enc = np.tanh(g.standard_normal((t_enc, dims))).astype(np.float32)
+    proj = (0.5 * g.standard_normal((t_enc, dims))).astype(np.float32)
+    return enc, proj
