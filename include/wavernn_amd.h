@@ -845,6 +845,72 @@ int wrnn_taco_run(const wrnn_taco_cfg *cfg, const wrnn_taco_weights *w, const fl
                   const int32_t *t_enc, int t_max, int rows, int r, float stop_threshold, int step_cap, int n_steps,
                   float *state, float *mel, float *attn, float *scratch, int timeout_ms, void *stream);
 
+/* ---- Tacotron CBHGs for ragged lists (csrc/cbhg.hip) -------------------------------
+ * The reference's Encoder (embedding, eval-mode prenet, CBHG) with encoder_proj, and its postnet
+ * CBHG with post_proj (models/tacotron.py), for n_seq sentences of n_seq lengths packed end to end
+ * on the time axis: position p of the packed axis is row p of every [positions][channels] buffer,
+ * and sentence i owns positions offsets[i] .. offsets[i + 1] − 1.  Stages are separate launches on
+ * the caller's stream; no workgroup waits for another.  fp32 weights, fp32 accumulation; a
+ * sentence's values do not depend on the other sentences, on its slot or on n_seq, bit for bit.
+ * Stateless: errors leave their text in wrnn_cond_last_error.  Two size sets are taken (the
+ * reference's hparams); anything else is WRNN_EUNSUPPORTED. */
+typedef struct {
+    int32_t K;            /* bank kernels 1..K: 16 (encoder) / 8 (postnet) */
+    int32_t in_channels;  /* 128 / 80 */
+    int32_t channels;     /* 128 */
+    int32_t proj1;        /* 128 / 256 */
+    int32_t proj2;        /* 128 / 80 (= in_channels: the residual) */
+    int32_t pre_highway;  /* 0 / 1: the bias-free proj2 → channels linear */
+    int32_t highways;     /* 4 */
+    int32_t front;        /* 1: the input is int32 ids (embedding, prenet fc1 → ReLU → fc2 → ReLU) / 0: float rows */
+    int32_t embed_dims;   /* 256 / 0 */
+    int32_t num_chars;    /* rows of the embedding (any >= 1) / 0 */
+    int32_t prenet_fc1;   /* 256 / 0 */
+    int32_t tail_out;     /* outputs of the bias-free tail over the GRU output: 256 (encoder_proj) / fft_bins 80 (post_proj) */
+} wrnn_cbhg_cfg;
+
+#define WRNN_CBHG_MAX_K 16
+#define WRNN_CBHG_HIGHWAYS 4
+/* Device pointers to the module's own contiguous fp32 tensors, PyTorch layouts (conv [out][in][k],
+ * linear [out][in]); read by every call, nothing is cached.  Entries beyond K, and the front's /
+ * pre_highway's where the cfg has none, are ignored. */
+typedef struct {
+    const float *embedding, *prenet_fc1_w, *prenet_fc1_b, *prenet_fc2_w, *prenet_fc2_b;
+    const float *bank_w[WRNN_CBHG_MAX_K], *bank_bn_w[WRNN_CBHG_MAX_K], *bank_bn_b[WRNN_CBHG_MAX_K];
+    const float *bank_bn_mean[WRNN_CBHG_MAX_K], *bank_bn_var[WRNN_CBHG_MAX_K];
+    const float *proj1_w, *proj1_bn_w, *proj1_bn_b, *proj1_bn_mean, *proj1_bn_var;
+    const float *proj2_w, *proj2_bn_w, *proj2_bn_b, *proj2_bn_mean, *proj2_bn_var;
+    const float *pre_highway_w;
+    const float *hw_w1[WRNN_CBHG_HIGHWAYS], *hw_b1[WRNN_CBHG_HIGHWAYS], *hw_w2[WRNN_CBHG_HIGHWAYS], *hw_b2[WRNN_CBHG_HIGHWAYS];
+    const float *rnn_w_ih, *rnn_w_hh, *rnn_b_ih, *rnn_b_hh;          /* forward direction, gates r z n */
+    const float *rnn_w_ih_r, *rnn_w_hh_r, *rnn_b_ih_r, *rnn_b_hh_r;  /* reverse direction */
+    const float *tail_w;
+} wrnn_cbhg_weights;
+
+/* WRNN_OK when the kernels take these sizes, else WRNN_EUNSUPPORTED with the reason. */
+int wrnn_cbhg_supported(const wrnn_cbhg_cfg *cfg);
+/* Bytes of device scratch a run over `positions` packed positions needs (any n_seq <= positions). */
+int64_t wrnn_cbhg_scratch_bytes(const wrnn_cbhg_cfg *cfg, int64_t positions);
+/* Offsets, in floats from the scratch's start, of the stage buffers that are intact after a run, in
+ * this order (−1: the cfg has no such stage): front output [positions][in_channels], bank
+ * [positions][K·channels] (ReLU and BatchNorm applied), pooled bank (same shape), conv_project1
+ * output [positions][proj1], highway-stack input before pre_highway (conv_project2 + residual)
+ * [positions][proj2], highway input [positions][channels] (the same buffer without pre_highway),
+ * highway output [positions][channels], GRU input terms [positions][6·channels], GRU output
+ * [positions][2·channels]. */
+#define WRNN_CBHG_STAGES 9
+int wrnn_cbhg_scratch_layout(const wrnn_cbhg_cfg *cfg, int64_t positions, int64_t *offsets);
+/* One pass over n_seq sentences.  `offsets` is a HOST array of n_seq + 1 entries, offsets[0] = 0,
+ * strictly increasing (every sentence has a position); `input` is device memory: int32 ids
+ * [positions] with the front, else float [positions][in_channels].  out_rnn [positions][2·channels]
+ * (may be NULL) and out_proj [positions][tail_out] are device buffers.  Everything is checked
+ * before anything is queued (WRNN_EINVAL): null or misaligned (16 bytes) pointers, n_seq < 1, the
+ * offsets, scratch_bytes below wrnn_cbhg_scratch_bytes, an id outside the embedding (the ids are
+ * read back for that).  Synchronises `stream` once before the stages are queued (the position
+ * tables' upload) and not after them. */
+int wrnn_cbhg_run(const wrnn_cbhg_cfg *cfg, const wrnn_cbhg_weights *w, const void *input, const int32_t *offsets,
+                  int n_seq, float *out_rnn, float *out_proj, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* Message of the last failed stateless call on this thread. */
 const char *wrnn_cond_last_error(void);
 

@@ -21,7 +21,15 @@ work is timed between device events, end-to-end rows by the host clock around a 
 µs per decoder step: `hip_us_per_step` is loop time / decoder steps of the launch (all rows advance
 together; the session's set-up — buffers, padding copies — is inside; `hip_launch_only_*` times
 wrnn_taco_run alone on sessions set up beforehand), `hip_us_per_sentence_step` divides that by N; `torch_us_per_sentence_step` is the eager
-loop's. `decoder_share` is the hip decoder's share of the `list` wall time. One JSON line per N."""
+loop's. `decoder_share` is the hip decoder's share of the `list` wall time. One JSON line per N.
+
+    python tools/tts_throughput.py --cbhg [--n ...] [--out profiles/tts_cbhg_throughput.json]
+
+`--cbhg` times the CBHG legs both ways in the same run, same protocol: the encoders of the N sentences
+(`[encode(x)]` under repeatable_modules against one `encode_list(cbhg='hip')`), their postnets on the
+HIP decoder's mels (`[postprocess(m)]` against `postprocess_list(cbhg='hip')`) and `synthesize_list`
+with `cbhg=None` and `cbhg='hip'` (host clock). `hip_min_call_ms` is a one-id `encode_list`: the
+per-call floor (id check, table upload, weight repack of the whole encoder, 18 launches)."""
 import argparse
 import json
 import os
@@ -64,6 +72,55 @@ def median(fn, reps, timer):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def cbhg_rows(args, tts, voc, vd):
+    """The --cbhg table: torch and hip legs of the encoder, the postnet and synthesize_list."""
+    d = syn.DEFAULT_TACOTRON
+    rows = []
+    one_id = [syn.make_text_ids(1, d.num_chars, seed=0)]
+    for N in args.n:
+        rng = np.random.default_rng(1000 + N)
+        xs = [syn.make_text_ids(int(t), d.num_chars, seed=i) for i, t in enumerate(rng.integers(20, 121, size=N))]
+        note = lambda what: print(f"# n={N}: {what}", file=sys.stderr, flush=True)   # noqa: E731
+        with torch.no_grad():
+            note("encoder")
+            with repeatable_modules():
+                enc_t = median(lambda: [tts.encode(x) for x in xs], args.reps, device_ms)
+            enc_h = median(lambda: tts.encode_list(xs, cbhg="hip"), args.reps, device_ms)
+            floor = median(lambda: tts.encode_list(one_id, cbhg="hip"), args.reps, device_ms)
+            coded = tts.encode_list(xs, cbhg="hip")
+            order = sorted(range(N), key=lambda i: -coded[i][0].shape[1])
+            mels = []
+            for k in range(0, N, MAX_ROWS):
+                idx = order[k:k + MAX_ROWS]
+                s = DecoderSession(tts, [coded[i][0][0] for i in idx], [coded[i][1][0] for i in idx], args.steps)
+                s.run(s.step_cap)
+                mels += [m.transpose(0, 1).unsqueeze(0).contiguous() for m, _, _ in s.outputs()]
+            note("postnet")
+            with repeatable_modules():
+                post_t = median(lambda: [tts.postprocess(m) for m in mels], args.reps, device_ms)
+            post_h = median(lambda: tts.postprocess_list(mels, cbhg="hip"), args.reps, device_ms)
+        row = {"n": N, "steps": args.steps, "reps": args.reps, "positions_encoder": int(sum(len(x) for x in xs)),
+               "positions_postnet": int(sum(m.shape[2] for m in mels)),
+               "encoder_torch_ms": round(enc_t[0], 3), "encoder_hip_ms": round(enc_h[0], 3),
+               "encoder_hip_ms_min_max": [round(enc_h[1], 3), round(enc_h[2], 3)],
+               "encoder_speedup": round(enc_t[0] / enc_h[0], 2),
+               "postnet_torch_ms": round(post_t[0], 3), "postnet_hip_ms": round(post_h[0], 3),
+               "postnet_hip_ms_min_max": [round(post_h[1], 3), round(post_h[2], 3)],
+               "postnet_speedup": round(post_t[0] / post_h[0], 2), "hip_min_call_ms": round(floor[0], 3)}
+        if not args.no_vocoder:
+            note("synthesize_list")
+            lst_t = median(lambda: gt.synthesize_list(tts, voc, xs, seed=1, steps=args.steps), args.reps, wall_ms)
+            lst_h = median(lambda: gt.synthesize_list(tts, voc, xs, seed=1, steps=args.steps, cbhg="hip"), args.reps, wall_ms)
+            row.update({"list_torch_ms": round(lst_t[0], 1), "list_hip_ms": round(lst_h[0], 1),
+                        "list_hip_ms_min_max": [round(lst_h[1], 1), round(lst_h[2], 1)],
+                        "list_speedup": round(lst_t[0] / lst_h[0], 2),
+                        "encoder_share_torch": round(enc_t[0] / lst_t[0], 3), "postnet_share_torch": round(post_t[0] / lst_t[0], 3),
+                        "encoder_share_hip": round(enc_h[0] / lst_h[0], 3), "postnet_share_hip": round(post_h[0] / lst_h[0], 3)})
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--n", type=int, nargs="+", default=[1, 24, 128, 512])
@@ -72,6 +129,7 @@ def main(argv=None):
     ap.add_argument("--torch-sample", type=int, default=8)
     ap.add_argument("--single-sample", type=int, default=4)
     ap.add_argument("--no-vocoder", action="store_true", help="skip the list / single rows")
+    ap.add_argument("--cbhg", action="store_true", help="time the encoder, postnet and list legs through torch and through hip")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     dev = torch.device("cuda")
@@ -86,8 +144,8 @@ def main(argv=None):
     voc.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in syn.make_fatchord_state(vd, 0).items()})
     voc.eval()
     n_dec = -(-args.steps // tts.r)
-    rows = []
-    for N in args.n:
+    rows = cbhg_rows(args, tts, voc, vd) if args.cbhg else []
+    for N in ([] if args.cbhg else args.n):
         rng = np.random.default_rng(1000 + N)
         xs = [syn.make_text_ids(int(t), d.num_chars, seed=i) for i, t in enumerate(rng.integers(20, 121, size=N))]
         note = lambda what: print(f"# n={N}: {what}", file=sys.stderr, flush=True)   # noqa: E731

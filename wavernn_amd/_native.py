@@ -28,7 +28,8 @@ EXPORTS = ("wrnn_create", "wrnn_set_weights", "wrnn_generate", "wrnn_check", "wr
            "wrnn_stream_open_rows", "wrnn_upsample_pack_window", "wrnn_upsample_window_frames",
            "wrnn_melspec_frames", "wrnn_melspec_table_floats", "wrnn_melspec_tables", "wrnn_melspec",
            "wrnn_melspec_window", "wrnn_melspec_windows", "wrnn_melspec_plan", "wrnn_taco_supported",
-           "wrnn_taco_state_floats", "wrnn_taco_state_layout", "wrnn_taco_scratch_floats", "wrnn_taco_run")
+           "wrnn_taco_state_floats", "wrnn_taco_state_layout", "wrnn_taco_scratch_floats", "wrnn_taco_run",
+           "wrnn_cbhg_supported", "wrnn_cbhg_scratch_bytes", "wrnn_cbhg_scratch_layout", "wrnn_cbhg_run")
 MELSPEC_SCRATCH_PER_SIGNAL = 64
 
 
@@ -56,6 +57,26 @@ class TacoCfg(ctypes.Structure):
 
 class TacoWeights(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in TACO_WEIGHTS]
+
+
+CBHG_MAX_K, CBHG_HIGHWAYS = 16, 4
+CBHG_STAGES = ("front", "bank", "pooled", "proj1", "residual", "highway_in", "highway_out", "gi", "rnn")
+
+
+class CbhgCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("K", "in_channels", "channels", "proj1", "proj2", "pre_highway", "highways",
+                                              "front", "embed_dims", "num_chars", "prenet_fc1", "tail_out")]
+
+
+class CbhgWeights(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("embedding", "prenet_fc1_w", "prenet_fc1_b", "prenet_fc2_w", "prenet_fc2_b")] + \
+        [(n, ctypes.c_void_p * CBHG_MAX_K) for n in ("bank_w", "bank_bn_w", "bank_bn_b", "bank_bn_mean", "bank_bn_var")] + \
+        [(n, ctypes.c_void_p) for n in ("proj1_w", "proj1_bn_w", "proj1_bn_b", "proj1_bn_mean", "proj1_bn_var",
+                                        "proj2_w", "proj2_bn_w", "proj2_bn_b", "proj2_bn_mean", "proj2_bn_var")] + \
+        [("pre_highway_w", ctypes.c_void_p)] + \
+        [(n, ctypes.c_void_p * CBHG_HIGHWAYS) for n in ("hw_w1", "hw_b1", "hw_w2", "hw_b2")] + \
+        [(n, ctypes.c_void_p) for n in ("rnn_w_ih", "rnn_w_hh", "rnn_b_ih", "rnn_b_hh", "rnn_w_ih_r", "rnn_w_hh_r",
+                                        "rnn_b_ih_r", "rnn_b_hh_r", "tail_w")]
 
 
 class WrnnError(RuntimeError):
@@ -238,6 +259,16 @@ def lib() -> ctypes.CDLL:
     L.wrnn_taco_run.argtypes = [ptc, ctypes.POINTER(TacoWeights), vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp,
                                 i32, vp]
     L.wrnn_taco_run.restype = i32
+    pcc = ctypes.POINTER(CbhgCfg)
+    L.wrnn_cbhg_supported.argtypes = [pcc]
+    L.wrnn_cbhg_supported.restype = i32
+    L.wrnn_cbhg_scratch_bytes.argtypes = [pcc, i64]
+    L.wrnn_cbhg_scratch_bytes.restype = i64
+    L.wrnn_cbhg_scratch_layout.argtypes = [pcc, i64, pi64]
+    L.wrnn_cbhg_scratch_layout.restype = i32
+    # cfg, weights, input (device), offsets (host, n_seq + 1), n_seq, out_rnn, out_proj, scratch, scratch_bytes, stream
+    L.wrnn_cbhg_run.argtypes = [pcc, ctypes.POINTER(CbhgWeights), vp, pi, i32, vp, vp, vp, i64, vp]
+    L.wrnn_cbhg_run.restype = i32
     L.wrnn_cond_last_error.argtypes = []
     L.wrnn_cond_last_error.restype = ctypes.c_char_p
     _lib = L

@@ -10,9 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "_lib", "libwavernn_amd.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("fatchord_loop.hip", "fatchord_split.hip", "fatchord_xcd.hip", "fatchord_xcds.hip", "fatchord_xcdm.hip", "fatchord_rows.hip", "deepmind_rows.hip", "deepmind_xcd.hip", "condition.hip", "frame_terms.hip", "melresnet.hip", "melspec.hip", "tacotron_decoder.hip", "capi.cpp", "capi_loops.cpp", "capi_lists.cpp", "capi_stream.cpp", "capi_taco.cpp")]
+SOURCES = [os.path.join(CSRC, f) for f in ("fatchord_loop.hip", "fatchord_split.hip", "fatchord_xcd.hip", "fatchord_xcds.hip", "fatchord_xcdm.hip", "fatchord_rows.hip", "deepmind_rows.hip", "deepmind_xcd.hip", "condition.hip", "frame_terms.hip", "melresnet.hip", "melspec.hip", "tacotron_decoder.hip", "cbhg.hip", "capi.cpp", "capi_loops.cpp", "capi_lists.cpp", "capi_stream.cpp", "capi_taco.cpp", "capi_cbhg.cpp")]
 HEADERS = [os.path.join(CSRC, f) for f in ("fatchord_loop.h", "fatchord_split.h", "fatchord_xcd.h", "fatchord_xcds.h", "fatchord_xcdm.h", "deepmind_xcd.h", "mfma_device.h", "xcd_device.h", "fatchord_rows.h", "deepmind_rows.h", "wrnn_device.h", "frame_terms.h",
-                                           "rows_device.h", "condition.h", "host_ctx.h", "tacotron_decoder.h")] + \
+                                           "rows_device.h", "condition.h", "host_ctx.h", "tacotron_decoder.h", "cbhg.h")] + \
     [os.path.join(REPO, "include", "wavernn_amd.h")]
 ARCH = os.environ.get("WRNN_OFFLOAD_ARCH", "gfx950")
 

@@ -19,7 +19,7 @@ synthesises encoded sentences from a Tacotron checkpoint:
     python -m wavernn_amd.gen_tacotron -m mel0.npy mel1.npy [-b|-u] [-t T] [-o O]
                                        [--voc_weights W.pyt] [--hp_file hparams.py]
                                        [--tts_k K] [--out_dir DIR] [--names a b ...]
-    python -m wavernn_amd.gen_tacotron --tts_weights T.pyt --sequences ids.txt|ids.npy [...]
+    python -m wavernn_amd.gen_tacotron --tts_weights T.pyt --sequences ids.txt|ids.npy [--cbhg torch|hip] [...]
 
 `--sequences` is a .npy of integer ids (1-D: one sentence; 2-D: one sentence per row) or a text file
 with one line of integer ids per sentence. With `--sequences` the sentences go through
@@ -88,13 +88,16 @@ def synthesize(tts_model, voc_model, inputs: Sequence, out_dir: Path, batched: b
 
 def synthesize_list(tts_model, voc_model, inputs: Sequence, out_dir: Optional[Path] = None, tts_k: int = 0,
                     standard_names: Optional[Sequence[str]] = None, seed: Optional[int] = None, steps: int = 2000,
-                    save_attention: Optional[Callable] = None) -> List[np.ndarray]:
+                    save_attention: Optional[Callable] = None, cbhg: Optional[str] = None) -> List[np.ndarray]:
     """All sentences at once: `tts_model.generate_list(inputs)` (one decoder launch per 128
     sentences), the :147-148 rescale of the second returned array as the reference takes it, then
     `voc_model.generate_list(mels, wide=True)`. With `out_dir` the waveforms are saved under the
-    names `synthesize()` would give them. Returns the waveforms in the order of `inputs`."""
+    names `synthesize()` would give them. `cbhg` ('torch' / 'hip') is handed to `generate_list` when given:
+    'hip' runs the list's encoders and postnets as ragged HIP passes. Returns the waveforms in the order
+    of `inputs`."""
     from .dsp import save_wav
-    triples = tts_model.generate_list(list(inputs), steps=steps)
+    kw = {} if cbhg is None else {'cbhg': cbhg}
+    triples = tts_model.generate_list(list(inputs), steps=steps, **kw)
     mels = [tacotron_mel_to_vocoder(m) for _, m, _ in triples]
     wavs = voc_model.generate_list(mels, seed=seed, wide=True)
     if out_dir is not None:
@@ -164,6 +167,8 @@ def main(argv=None):
     ap.add_argument('--names', nargs='*', default=None, help='output names (hp.test_sentences_names)')
     ap.add_argument('--out_dir', default='.')
     ap.add_argument('--seed', type=int, default=None)
+    ap.add_argument('--cbhg', choices=('torch', 'hip'), default=None,
+                    help='with --sequences: the Tacotron encoder / postnet CBHGs as torch modules (default) or ragged HIP passes')
     ap.set_defaults(batched=None)
     args = ap.parse_args(argv)
     hp = HParams().configure(args.hp_file)
@@ -189,7 +194,7 @@ def main(argv=None):
         from .tacotron import build_tacotron
         tts = build_tacotron(hp, weights=args.tts_weights, device=torch.device('cuda'))
         synthesize_list(tts, voc, seqs, Path(args.out_dir), tts_k=args.tts_k or tts.get_step() // 1000,
-                        standard_names=args.names, seed=args.seed)
+                        standard_names=args.names, seed=args.seed, cbhg=args.cbhg)
         print('\n\nDone.\n')
         return
     tts = _SavedMels(args.mels, hp.num_mels)

@@ -345,12 +345,20 @@ def tacotron_state_shapes(d: TacotronDims) -> Dict[str, Tuple[tuple, str]]:
     return s
 
 
+def is_cbhg_gate_matrix(key: str) -> bool:
+    """The matrices that drive the gates of the two CBHGs: the bidirectional GRU's and the highways' W2."""
+    if not (key.startswith("encoder.cbhg.") or key.startswith("postnet.")):
+        return False
+    return ".rnn.weight_" in key or (".highways." in key and key.endswith(".W2.weight"))
+
+
 def make_tacotron_state(d: TacotronDims = DEFAULT_TACOTRON, seed: int = 0, scale: float = 1.0, r: int = 2,
-                        step: int = 180_000) -> Dict[str, np.ndarray]:
+                        step: int = 180_000, cbhg_gate_scale: float = 1.0) -> Dict[str, np.ndarray]:
     """Random Tacotron weights in the reference layout: matrices xavier-uniform (the reference's init),
     biases U(±0.1), BatchNorm statistics in a plausible range, the embedding N(0, 1); the decoder's
-    matrices are multiplied by `scale` (1 tame, 2 lively, 3-4 saturated attention and gates). One
-    independent stream per key."""
+    matrices are multiplied by `scale` (1 tame, 2 lively, 3-4 saturated attention and gates), the CBHGs'
+    gate matrices (is_cbhg_gate_matrix) by `cbhg_gate_scale` (1 tame, 5 hot: saturated GRU and highway
+    gates). One independent stream per key."""
     shapes = tacotron_state_shapes(d)
     out: Dict[str, np.ndarray] = {}
     for key in sorted(shapes):
@@ -368,7 +376,8 @@ def make_tacotron_state(d: TacotronDims = DEFAULT_TACOTRON, seed: int = 0, scale
             rf = float(np.prod(shape[2:])) if len(shape) > 2 else 1.0
             bound = np.sqrt(6.0 / ((shape[0] + shape[1]) * rf))
             w = g.uniform(-bound, bound, size=shape)
-            out[key] = (w * (scale if kind == "xd" else 1.0)).astype(np.float32)
+            mult = scale if kind == "xd" else (cbhg_gate_scale if is_cbhg_gate_matrix(key) else 1.0)
+            out[key] = (w * mult).astype(np.float32)
         elif kind == "emb":
             out[key] = g.standard_normal(shape).astype(np.float32)
         elif kind == "b":
@@ -389,6 +398,11 @@ def make_tacotron_state(d: TacotronDims = DEFAULT_TACOTRON, seed: int = 0, scale
 def make_text_ids(n: int, num_chars: int = 148, seed: int = 5) -> np.ndarray:
     """n symbol ids in [1, num_chars) — a text_to_sequence output of length n."""
     return np.random.default_rng([seed, n]).integers(1, num_chars, size=n).astype(np.int64)
+
+
+def make_taco_mel(frames: int, n_mels: int = 80, seed: int = 9) -> np.ndarray:
+    """(n_mels, frames) float32 ~ 2·N(0, 1): a decoder output in the lively regime's range."""
+    return (2.0 * np.random.default_rng([seed, frames, n_mels]).standard_normal((n_mels, frames))).astype(np.float32)
 
 
 def make_encoder_seq(t_enc: int, dims: int = 256, seed: int = 7):

@@ -16,6 +16,12 @@ Two backends compute the same thing:
   DESIGN.md §4.9). The encoder, `encoder_proj`, the postnet CBHG and `post_proj` run once per
   sentence, parallel over time, as torch-ROCm modules.
 
+``cbhg='hip'`` (opt-in, independent of `backend`; also `encode_list`, `postprocess_list`) runs those
+two CBHGs as ragged HIP passes instead (csrc/cbhg.hip): all sentences of a list packed
+end to end on the time axis, one `wrnn_cbhg_run` for the encoders and one for the postnets per chunk
+of `cbhg_budget` bytes of scratch. With `backend='hip'` as well no torch module runs and torch's
+deterministic switches (below) are not touched. ``cbhg=None`` / ``'torch'`` is the path described here.
+
 `generate()` runs in eval mode: no prenet dropout, no zoneout; the loop is deterministic.
 The text front end (`text_to_sequence`) stays with the caller: inputs are sequences of ids.
 While a call runs, the encoder and postnet modules run under torch's process-wide deterministic-algorithm
@@ -37,6 +43,8 @@ import torch.nn.functional as F
 
 MAX_ROWS = 128          # sentences per launch: the vocoder's slot count
 BACKENDS = (None, 'torch', 'hip')
+CBHGS = (None, 'torch', 'hip')
+CBHG_SCRATCH_BUDGET = 1 << 30   # bytes of device scratch one ragged CBHG pass may take before a list is cut into chunks
 
 
 @contextlib.contextmanager
@@ -374,6 +382,145 @@ class Tacotron(nn.Module):
             raise RuntimeError(f"backend='hip' cannot run this model: {why}")
         return 'torch'
 
+    # ------------------------------------------------------------------ the HIP CBHGs' view
+    def cbhg_cfg(self, which: str):
+        """The wrnn_cbhg_cfg of 'encoder' or 'postnet'."""
+        from . import _native as nat
+        enc = which == 'encoder'
+        c = self.encoder.cbhg if enc else self.postnet
+        e = self.encoder
+        return nat.CbhgCfg(len(c.conv1d_bank), c.conv1d_bank[0].conv.in_channels, c.conv1d_bank[0].conv.out_channels,
+                           c.conv_project1.conv.out_channels, c.conv_project2.conv.out_channels, int(c.highway_mismatch),
+                           len(c.highways), int(enc), e.embedding.embedding_dim if enc else 0,
+                           e.embedding.num_embeddings if enc else 0, e.pre_net.fc1.out_features if enc else 0,
+                           (self.encoder_proj if enc else self.post_proj).out_features)
+
+    def cbhg_weights(self, which: str):
+        """(wrnn_cbhg_weights, the tensors it points to): the module's own tensors, collected per call,
+        so .data updates, reloads and changed BatchNorm statistics reach the kernels."""
+        from . import _native as nat
+        enc = which == 'encoder'
+        c = self.encoder.cbhg if enc else self.postnet
+        keep: List[torch.Tensor] = []
+
+        def ptr(t):
+            t = t.detach().to(torch.float32).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        w = nat.CbhgWeights()
+        if enc:
+            e = self.encoder
+            w.embedding, w.prenet_fc1_w, w.prenet_fc1_b = ptr(e.embedding.weight), ptr(e.pre_net.fc1.weight), ptr(e.pre_net.fc1.bias)
+            w.prenet_fc2_w, w.prenet_fc2_b = ptr(e.pre_net.fc2.weight), ptr(e.pre_net.fc2.bias)
+
+        def bnconv(m):
+            return (ptr(m.conv.weight), ptr(m.bnorm.weight), ptr(m.bnorm.bias), ptr(m.bnorm.running_mean),
+                    ptr(m.bnorm.running_var))
+        for k, m in enumerate(c.conv1d_bank):
+            w.bank_w[k], w.bank_bn_w[k], w.bank_bn_b[k], w.bank_bn_mean[k], w.bank_bn_var[k] = bnconv(m)
+        w.proj1_w, w.proj1_bn_w, w.proj1_bn_b, w.proj1_bn_mean, w.proj1_bn_var = bnconv(c.conv_project1)
+        w.proj2_w, w.proj2_bn_w, w.proj2_bn_b, w.proj2_bn_mean, w.proj2_bn_var = bnconv(c.conv_project2)
+        if c.highway_mismatch:
+            w.pre_highway_w = ptr(c.pre_highway.weight)
+        for i, h in enumerate(c.highways):
+            w.hw_w1[i], w.hw_b1[i], w.hw_w2[i], w.hw_b2[i] = ptr(h.W1.weight), ptr(h.W1.bias), ptr(h.W2.weight), ptr(h.W2.bias)
+        r = c.rnn
+        w.rnn_w_ih, w.rnn_w_hh, w.rnn_b_ih, w.rnn_b_hh = ptr(r.weight_ih_l0), ptr(r.weight_hh_l0), ptr(r.bias_ih_l0), ptr(r.bias_hh_l0)
+        w.rnn_w_ih_r, w.rnn_w_hh_r = ptr(r.weight_ih_l0_reverse), ptr(r.weight_hh_l0_reverse)
+        w.rnn_b_ih_r, w.rnn_b_hh_r = ptr(r.bias_ih_l0_reverse), ptr(r.bias_hh_l0_reverse)
+        w.tail_w = ptr((self.encoder_proj if enc else self.post_proj).weight)
+        return w, keep
+
+    def cbhg_unsupported_reason(self) -> Optional[str]:
+        """None when cbhg='hip' can run this model where it is, else why not."""
+        p = self.encoder_proj.weight
+        if p.device.type != 'cuda':
+            return 'the model is not on a GPU'
+        if p.dtype != torch.float32:
+            return f'the kernels take float32 weights, the model is {p.dtype}'
+        from . import _native as nat
+        for which in ('encoder', 'postnet'):
+            c = self.encoder.cbhg if which == 'encoder' else self.postnet
+            if len(c.conv1d_bank) > nat.CBHG_MAX_K or len(c.highways) > nat.CBHG_HIGHWAYS:
+                return f'the {which} CBHG has {len(c.conv1d_bank)} bank kernels and {len(c.highways)} highways; at most ' \
+                       f'{nat.CBHG_MAX_K} and {nat.CBHG_HIGHWAYS} are taken'
+            cfg = self.cbhg_cfg(which)
+            if nat.lib().wrnn_cbhg_supported(ctypes.byref(cfg)) != 0:
+                return f'{which}: ' + (nat.lib().wrnn_cond_last_error() or b'').decode(errors='replace')
+        return None
+
+    def _cbhg(self, cbhg) -> str:
+        if cbhg not in CBHGS:
+            raise ValueError(f'cbhg must be one of {CBHGS}, got {cbhg!r}')
+        if cbhg != 'hip':
+            return 'torch'
+        why = self.cbhg_unsupported_reason()
+        if why is not None:
+            raise RuntimeError(f"cbhg='hip' cannot run this model: {why}")
+        return 'hip'
+
+    def _cbhg_run_list(self, which: str, rows: Sequence[torch.Tensor], budget: Optional[int], keep_scratch: Optional[list] = None):
+        """`rows`: per sentence int32 ids (T,) or float rows (T, in_channels) on the device. One wrnn_cbhg_run
+        per chunk of whole sentences whose scratch stays within `budget` bytes (a sentence that alone
+        exceeds it runs alone). Returns per sentence (GRU output (T, 2·channels), tail output (T, tail)).
+        `keep_scratch`: a list that receives (cfg, scratch tensor, positions) of every run, for reading stages."""
+        from . import _native as nat
+        L = nat.lib()
+        cfg = self.cbhg_cfg(which)
+        budget = CBHG_SCRATCH_BUDGET if budget is None else int(budget)
+        dev = self.encoder_proj.weight.device
+        lens = [int(r.shape[0]) for r in rows]
+        if min(lens, default=1) < 1:
+            raise ValueError('every sentence needs at least one position')
+        need = lambda p: int(L.wrnn_cbhg_scratch_bytes(ctypes.byref(cfg), p))   # noqa: E731
+        out: list = [None] * len(rows)
+        k = 0
+        while k < len(rows):
+            n, pos = 1, lens[k]
+            while k + n < len(rows) and need(pos + lens[k + n]) <= budget:
+                pos += lens[k + n]
+                n += 1
+            nbytes = need(pos)
+            if nbytes < 0:
+                nat.check_cond(nbytes)
+            offs = (ctypes.c_int * (n + 1))(*np.concatenate([[0], np.cumsum(lens[k:k + n])]).tolist())
+            packed = torch.cat(list(rows[k:k + n]), dim=0).contiguous()
+            scratch = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+            rnn = torch.empty(pos, 2 * cfg.channels, device=dev, dtype=torch.float32)
+            tail = torch.empty(pos, cfg.tail_out, device=dev, dtype=torch.float32)
+            w, keep = self.cbhg_weights(which)
+            rc = L.wrnn_cbhg_run(ctypes.byref(cfg), ctypes.byref(w), packed.data_ptr(), offs, n, rnn.data_ptr(), tail.data_ptr(),
+                                 scratch.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+            del keep
+            nat.check_cond(rc)
+            if keep_scratch is not None:
+                keep_scratch.append((cfg, scratch, pos))
+            for i in range(n):
+                out[k + i] = (rnn[offs[i]:offs[i + 1]], tail[offs[i]:offs[i + 1]])
+            k += n
+        return out
+
+    def encode_list(self, xs: Sequence, cbhg: Optional[str] = None, cbhg_budget: Optional[int] = None) -> list:
+        """Per sentence (encoder_seq, encoder_seq_proj), each (1, T, decoder_dims). cbhg='hip': every
+        sentence's encoder in one ragged HIP pass per chunk (eval-mode arithmetic whatever the module's
+        mode); None / 'torch': encode() per sentence, in the module's current mode."""
+        if self._cbhg(cbhg) == 'torch':
+            return [self.encode(x) for x in xs]
+        dev = self.encoder_proj.weight.device
+        ids = [torch.as_tensor(np.asarray(x).reshape(-1) if not torch.is_tensor(x) else x.reshape(-1)).to(dev, torch.int32)
+               for x in xs]
+        return [(e.unsqueeze(0), p.unsqueeze(0)) for e, p in self._cbhg_run_list('encoder', ids, cbhg_budget)]
+
+    def postprocess_list(self, mels: Sequence[torch.Tensor], cbhg: Optional[str] = None,
+                         cbhg_budget: Optional[int] = None) -> list:
+        """Per mel (1, n_mels, frames) the linear (1, fft_bins, frames); cbhg as in encode_list."""
+        if self._cbhg(cbhg) == 'torch':
+            return [self.postprocess(m) for m in mels]
+        dev = self.encoder_proj.weight.device
+        rows = [torch.as_tensor(m).to(dev, torch.float32).reshape(self.n_mels, -1).t() for m in mels]
+        return [lin.t().unsqueeze(0) for _, lin in self._cbhg_run_list('postnet', rows, cbhg_budget)]
+
     # ------------------------------------------------------------------ generation
     def encode(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
         """One sentence's ids → (encoder_seq, encoder_seq_proj), each (1, T, decoder_dims)."""
@@ -402,9 +549,13 @@ class Tacotron(nn.Module):
     def _numpy(mel, linear, attn):
         return mel[0].cpu().numpy(), linear[0].cpu().numpy(), attn[0].cpu().numpy()
 
-    def generate(self, x, steps: int = 2000, backend: Optional[str] = None):
+    def generate(self, x, steps: int = 2000, backend: Optional[str] = None, cbhg: Optional[str] = None,
+                 cbhg_budget: Optional[int] = None):
         """(mel (n_mels, frames), linear (fft_bins, frames), attention (decoder_steps, T_enc)) as numpy,
-        in the reference's order and shapes."""
+        in the reference's order and shapes. cbhg='hip' runs the encoder and the postnet as ragged HIP
+        passes (csrc/cbhg.hip) instead of torch modules; it is independent of `backend`."""
+        if self._cbhg(cbhg) == 'hip':
+            return self.generate_list([x], steps, backend, cbhg='hip', cbhg_budget=cbhg_budget)[0]
         if self._backend(backend) == 'hip':
             return self.generate_list([x], steps)[0]
         self.eval()
@@ -416,9 +567,14 @@ class Tacotron(nn.Module):
         finally:
             self.train()      # as the reference leaves the model, also when the call raised
 
-    def generate_list(self, xs: Sequence, steps: int = 2000, backend: Optional[str] = None) -> list:
+    def generate_list(self, xs: Sequence, steps: int = 2000, backend: Optional[str] = None, cbhg: Optional[str] = None,
+                      cbhg_budget: Optional[int] = None) -> list:
         """N sentences of N lengths; each stops on its own. Returns generate()'s triple per sentence,
-        in the order given."""
+        in the order given. cbhg='hip': the list's encoders are one ragged HIP pass and its postnets
+        another (per chunk of `cbhg_budget` bytes of scratch, default CBHG_SCRATCH_BUDGET); with
+        backend='hip' as well no torch module runs and torch's deterministic switches stay untouched."""
+        if self._cbhg(cbhg) == 'hip':
+            return self._generate_list_cbhg(xs, steps, self._backend(backend), cbhg_budget)
         if self._backend(backend) == 'torch':
             return [self.generate(x, steps, backend='torch') for x in xs]
         self.eval()
@@ -438,6 +594,34 @@ class Tacotron(nn.Module):
         finally:
             self.train()      # as the reference leaves the model, also when a launch failed (WRNN_ETIMEOUT, …)
         return out
+
+    def _generate_list_cbhg(self, xs: Sequence, steps: int, backend: str, budget: Optional[int]) -> list:
+        """generate_list with the CBHGs in HIP: encode_list → decoder loop (hip launches of up to 128
+        sentences, or the torch loop per sentence) → postprocess_list."""
+        if len(xs) == 0:
+            return []
+        self.eval()
+        mels: list = [None] * len(xs)
+        attns: list = [None] * len(xs)
+        try:
+            with torch.no_grad():
+                coded = self.encode_list(xs, cbhg='hip', cbhg_budget=budget)
+                if backend == 'hip':
+                    order = sorted(range(len(xs)), key=lambda i: -coded[i][0].shape[1])
+                    for k in range(0, len(order), MAX_ROWS):
+                        idx = order[k:k + MAX_ROWS]
+                        sess = DecoderSession(self, [coded[i][0][0] for i in idx], [coded[i][1][0] for i in idx], steps)
+                        sess.run(sess.step_cap)
+                        for i, (mel, attn, _) in zip(idx, sess.outputs()):
+                            mels[i], attns[i] = mel.transpose(0, 1).unsqueeze(0).contiguous(), attn.unsqueeze(0).clone()
+                else:
+                    with repeatable_modules():
+                        for i, (enc, proj) in enumerate(coded):
+                            mels[i], attns[i] = self.decode_torch(enc, proj, steps)
+                lins = self.postprocess_list(mels, cbhg='hip', cbhg_budget=budget)
+                return [self._numpy(m, l, a) for m, l, a in zip(mels, lins, attns)]
+        finally:
+            self.train()
 
 
 # the reference's hparams.py:67-77; an hparams object's own tts_* values take precedence
